@@ -3,15 +3,18 @@
 RK/AB substep -> pressure correction with the FFT Poisson solve), FP64, on N
 MI355X GPUs of one node.  Metric (BASELINE.json): DoF*steps/s, whole job.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full time step (3 substeps for RK3) of the 512^3-per-GPU TGV
 (BASELINE.json configs[2]; weak scaling: the global grid grows with N).
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
-`roofline` (dominant kernel: the fused transport-equation component, timed with
-HIP events inside the timed region) and `cpu_baseline` (the oracle restatement
-of the reference's OpenMP path on the host cores, bounded sample, N=1 only).
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype,
+ms_per_step (the time of one timed step) and the set-up.  A plain run does
+nothing but set up, warm up, time the steps (and write --dump-outputs).
+--full adds `roofline` (dominant kernel: the fused transport-equation component,
+timed with HIP events inside the timed region), `kernel_ms`, `cpu_baseline`
+(the oracle restatement of the reference's OpenMP path on the host cores,
+bounded sample, N=1 only) and `other_configs`.
 """
 import argparse
 import json
@@ -261,6 +264,29 @@ def live_traffic(kernel_substr, extra_args, timeout=120):
                    "FETCH x 2 (gfx950: 64 B counted per 128-B request, MI355X_MICROARCH.md)"}, None
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes in all (a field larger than its share is sampled)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(d, solver, rank, world):
+    """what the timed steps computed, as a caller of Solver.step receives it: the velocity u, v, w (arrays [nz, ny, nx]
+    of the library's real kind, float64 or float32), flattened, as DIR/u.npy, v.npy, w.npy (N > 1: u_rank<r>.npy ... per
+    rank, the budget shared).  A field larger than its share of DUMP_BYTES is written at the sorted flat indices of one
+    seeded draw -- the same points in every run of the same arguments, so that two builds compare point for point."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    idx = None
+    for name in ("u", "v", "w"):
+        a = solver.backend.get_field_data(getattr(solver, name)).reshape(-1)
+        k = DUMP_BYTES // (3 * world * a.itemsize)
+        if a.size > k:
+            if idx is None:
+                idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, k))
+            a = a[idx]
+        np.save(os.path.join(d, name + sfx + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N rank processes here, as FRESH children of a
     parent that has not touched the GPU (never re-exec a process that has), one per device, rendezvous on
@@ -348,9 +374,22 @@ def main():
     ap.add_argument("--lazy", action="store_true",
                     help="the reference's op sequence through the library's deferred execution (csrc/lazy.hip): what the "
                          "unchanged solver.f90 gets through the Fortran shim; implies --op-granular")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the roofline and per-kernel times (HIP-event timers in the timed region, "
+                         "one more step with every kernel class timed, rocprofv3 --pmc child runs), the CPU baselines, the "
+                         "other configurations and, at N > 1, the exchange / overlap report and the second layout; the "
+                         "--no-* options above leave parts of it out.  Without it a run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the velocity they left (u, v, w) as DIR/<name>.npy: whole fields up "
+                         "to %d MiB in all, else the same seeded sample of points in every run" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.lazy:
         args.op_granular = True
+    if not args.full:
+        args.no_cpu_baseline = args.no_other_configs = args.no_live_traffic = True
     if args.cpu_baseline_child:  # (never touches the GPU)
         print(json.dumps(cpu_baseline_child(args.cpu_n, args.cpu_steps)))
         return
@@ -495,9 +534,10 @@ def main():
         torch.cuda.synchronize()
         return
 
-    def measure(case, nproc_dir, dims, decomp_name):
-        """W warm-up steps, K timed steps between barriers + device syncs (max over the ranks), one more step with every
-        kernel class and the exchanges timed; returns the JSON object of this case on this decomposition"""
+    def measure(case, nproc_dir, dims, decomp_name, dump=True):
+        """W warm-up steps, K timed steps between barriers + device syncs (max over the ranks); --dump-outputs: what the
+        last timed step left (dump=True); --full: one more step with every kernel class and the exchanges timed.
+        Returns the JSON object of this case on this decomposition"""
         solver, backend = case.solver, case.solver.backend
         nstage = solver.time_integrator.nstage
 
@@ -511,18 +551,19 @@ def main():
         for _ in range(args.warmup):
             it += 1
             case.step(it)
-        # HIP-event timers around the launches of the dominant kernel class (the roofline's kernel) during the timed
-        # region; the other classes are timed in one extra step afterwards (all classes on cost 0.4 ms per step of
-        # event records: same-box A/B 48.4 -> 48.0)
-        backend.prof_enable(True)
-        backend.prof_select(None if os.environ.get("X3D_BENCH_PROF_ALL") == "1" else ("transeq_fwd", "transeq_bwd"))
-        backend.prof_reset()
-        backend.rk_fused_passes = 0
-        backend.rk_fused_launches = 0
-        backend.rk_in_tile3_passes = 0
-        backend.rk_in_tile3_launches = 0
-        tq3_before = int(backend.lib.x3d_backend_counter(backend.h, 0))
-        upd_before = int(backend.lib.x3d_backend_counter(backend.h, 1))
+        if args.full:
+            # HIP-event timers around the launches of the dominant kernel class (the roofline's kernel) during the timed
+            # region; the other classes are timed in one extra step afterwards (all classes on cost 0.4 ms per step of
+            # event records: same-box A/B 48.4 -> 48.0)
+            backend.prof_enable(True)
+            backend.prof_select(None if os.environ.get("X3D_BENCH_PROF_ALL") == "1" else ("transeq_fwd", "transeq_bwd"))
+            backend.prof_reset()
+            backend.rk_fused_passes = 0
+            backend.rk_fused_launches = 0
+            backend.rk_in_tile3_passes = 0
+            backend.rk_in_tile3_launches = 0
+            tq3_before = int(backend.lib.x3d_backend_counter(backend.h, 0))
+            upd_before = int(backend.lib.x3d_backend_counter(backend.h, 1))
         sync_all()
         t0 = time.perf_counter()
         for k in range(args.steps):
@@ -540,6 +581,84 @@ def main():
         value = dof_global * args.steps / elapsed
         # (bytes per DoF below are SURVEY 8(d)'s FP64 figures; the FP32 flavour of the library moves half of them)
         dofb = dof_local * (0.5 if os.environ.get("X3D_SINGLE_PREC") == "1" else 1.0)
+
+        def line(exchanges=None, overlap_report=None, roofline=None, prof=None):
+            """the JSON object: the headline figure and its set-up, + what --full measured"""
+            emu = None
+            if args.virtual_ranks:
+                emu = {"what": "EMULATION, not a multi-GPU measurement: ONE process on ONE GPU runs rank 0's kernels and exchange "
+                               "pattern of a %d-rank job; every peer is the rank itself through RCCL; every exchange holds its "
+                               "stream for the time the message would spend on xGMI links" % args.virtual_ranks,
+                       "virtual_ranks": args.virtual_ranks,
+                       "link_GBs_per_direction": float(os.environ["X3D_COMM_EMULATE_LINKS"]),
+                       "link_model": "all-to-all among n peers: bytes / n / rate (n - 1 links at once); neighbour exchange: "
+                                     "largest message / rate; 76.8 GB/s per link and direction by the public MI355X "
+                                     "specification (7 links x 153.6 GB/s bidirectional), 61.4 = 80 % of it",
+                       "value_if_every_rank_ran_like_this_one": value,
+                       "slab_yparts": getattr(backend.poisson_fft, "yparts", None),
+                       "slab_parts": getattr(backend.poisson_fft, "parts", None)}
+            out = {
+                "metric": ("DoF*steps/s (whole node), TGV 512^3 per GPU, full fractional step" if args.case == "tgv"
+                           else "DoF*steps/s, channel (stretched y, 010 Poisson), full fractional step")
+                          + (" -- EMULATED %d ranks on one GPU" % args.virtual_ranks if args.virtual_ranks else ""),
+                "emulation": emu,
+                "value": value, "unit": "DoF*steps/s", "n_gpus": args.gpus, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32" if os.environ.get("X3D_SINGLE_PREC") == "1" else "f64",
+                "data": "synthetic",
+                # results differ from the reference's OpenMP backend by FMA contraction and re-associated scans only: every
+                # -m gpu parity test holds 1e-12 relative per operator (1e-11 on traces / full steps, 1e-10 on the stretched
+                # 010 Poisson solve); the north star asks for 1e-6 on the enstrophy trace
+                "parity_tol": {"operators_rel": 1e-12, "full_step_rel": 1e-11, "poisson_010_rel": 1e-10,
+                               "north_star_enstrophy_rel": 1e-6},
+                "config": {"workload": (f"TGV {dims[0]}x{dims[1]}x{dims[2]} all-periodic, Re=1600, dt=1e-3, "
+                                        if args.case == "tgv" else
+                                        f"channel {dims[0]}x{dims[1]}x{dims[2]} verts, y Dirichlet + top-bottom "
+                                        f"stretching, Re=4200, dt=5e-3, rotation forcing, ")
+                                       + f"{args.time_intg} ({nstage} substeps/step), compact6/classic schemes, "
+                                       + ("no pressure solve (configs[1])" if args.no_poisson
+                                          else "rocFFT Poisson (configs[2])" if args.case == "tgv"
+                                          else "rocFFT Poisson 010, pentadiagonal spectral solve"),
+                           "per_gpu": f"{args.n}^3" if args.case == "tgv" else args.dims, "nproc_dir": list(nproc_dir),
+                           "driver": ("op-granular calls recorded and fused inside the library (deferred execution)" if args.lazy
+                                      else "op-granular" if args.op_granular else "fused"),
+                           "parallelism": f"domain decomposition {nproc_dir[0]}x{nproc_dir[1]}x{nproc_dir[2]}",
+                           # N > 1: did the overlapped exchange path pass its first-use check against the ordered path
+                           # (x3d2_amd/parallel.py, Comm.self_check; None: not exercised, e.g. one rank or host-staged)
+                           "overlap_self_check": getattr(comm, "self_check_result", None),
+                           "overlap_self_check_error": getattr(comm, "self_check_error", None),
+                       # (ms of two 2 ms spins: one on the candidate communication stream + one on the compute stream, both on
+                       # the compute stream) per candidate: equal = the candidate shares the compute stream's hardware queue
+                       # and was passed over (parallel.Comm._pick_stream)
+                       "comm_stream_probe_ms": getattr(comm, "stream_probe", None),
+                           # N > 1: which decomposition ran, and what its one-step validation (and any it replaced) showed
+                           "decomposition": decomp_name if args.case == "tgv" else "slabs",
+                           "decomposition_requested": requested,
+                           "decompositions_tried": tried or None,
+                           "transport": ("gloo, host staged (ranks share a GPU: a dry run)" if share else
+                                         "RCCL %s" % ".".join(str(v) for v in torch.cuda.nccl.version())) if world > 1 or
+                                        dist.is_initialized() else None,
+                           # exchanges of ONE step after the timed region, HIP events on the stream they were posted from:
+                           # sendrecv = halo rows + boundary values of the decomposed direction, alltoall = Poisson transposes
+                           "exchanges_one_step": exchanges,
+                           "overlap_report": overlap_report,
+                           # 000 solve at 512^3 on one rank: transforms ordered z, x, y with the z transforms inside the
+                           # neighbouring z operator pairs (csrc/zfirst.hip); counted pressure corrections of the fused driver
+                           "poisson_z_first": (int(case.solver.n_zfirst) if not args.lazy
+                                               else int(backend.lazy_stats().get("zfirst", 0)))},
+                "dof_substeps_per_s": value * nstage,
+            }
+            if roofline is not None:
+                out["roofline"] = roofline
+                out["kernel_ms"] = prof
+            if args.lazy:
+                out["lazy_stats"] = backend.lazy_stats()
+            return out
+
+        if args.dump_outputs and dump:
+            dump_outputs(args.dump_outputs, solver, rank, world)
+        if not args.full:
+            return line()
 
         # ---- roofline of the dominant kernel class: one transport-equation
         # component = k_transeq_fwd + k_transeq_bwd (64 B/DoF for the three
@@ -723,76 +842,7 @@ def main():
                         "added to and written), + the RK stage's fields where a z launch carries it",
                 "launches": lx + ly + lz + le, "ms": ph_ms, "bytes": comp,
                 "achieved": comp / (ph_ms * 1e-3) / 1e9, "frac": comp / (ph_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-
-        emu = None
-        if args.virtual_ranks:
-            emu = {"what": "EMULATION, not a multi-GPU measurement: ONE process on ONE GPU runs rank 0's kernels and exchange "
-                           "pattern of a %d-rank job; every peer is the rank itself through RCCL; every exchange holds its "
-                           "stream for the time the message would spend on xGMI links" % args.virtual_ranks,
-                   "virtual_ranks": args.virtual_ranks,
-                   "link_GBs_per_direction": float(os.environ["X3D_COMM_EMULATE_LINKS"]),
-                   "link_model": "all-to-all among n peers: bytes / n / rate (n - 1 links at once); neighbour exchange: "
-                                 "largest message / rate; 76.8 GB/s per link and direction by the public MI355X "
-                                 "specification (7 links x 153.6 GB/s bidirectional), 61.4 = 80 % of it",
-                   "value_if_every_rank_ran_like_this_one": value,
-                   "slab_yparts": getattr(backend.poisson_fft, "yparts", None),
-                   "slab_parts": getattr(backend.poisson_fft, "parts", None)}
-        out = {
-            "metric": ("DoF*steps/s (whole node), TGV 512^3 per GPU, full fractional step" if args.case == "tgv"
-                       else "DoF*steps/s, channel (stretched y, 010 Poisson), full fractional step")
-                      + (" -- EMULATED %d ranks on one GPU" % args.virtual_ranks if args.virtual_ranks else ""),
-            "emulation": emu,
-            "value": value, "unit": "DoF*steps/s", "n_gpus": args.gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32" if os.environ.get("X3D_SINGLE_PREC") == "1" else "f64",
-            "data": "synthetic",
-            # results differ from the reference's OpenMP backend by FMA contraction and re-associated scans only: every
-            # -m gpu parity test holds 1e-12 relative per operator (1e-11 on traces / full steps, 1e-10 on the stretched
-            # 010 Poisson solve); the north star asks for 1e-6 on the enstrophy trace
-            "parity_tol": {"operators_rel": 1e-12, "full_step_rel": 1e-11, "poisson_010_rel": 1e-10,
-                           "north_star_enstrophy_rel": 1e-6},
-            "config": {"workload": (f"TGV {dims[0]}x{dims[1]}x{dims[2]} all-periodic, Re=1600, dt=1e-3, "
-                                    if args.case == "tgv" else
-                                    f"channel {dims[0]}x{dims[1]}x{dims[2]} verts, y Dirichlet + top-bottom "
-                                    f"stretching, Re=4200, dt=5e-3, rotation forcing, ")
-                                   + f"{args.time_intg} ({nstage} substeps/step), compact6/classic schemes, "
-                                   + ("no pressure solve (configs[1])" if args.no_poisson
-                                      else "rocFFT Poisson (configs[2])" if args.case == "tgv"
-                                      else "rocFFT Poisson 010, pentadiagonal spectral solve"),
-                       "per_gpu": f"{args.n}^3" if args.case == "tgv" else args.dims, "nproc_dir": list(nproc_dir),
-                       "driver": ("op-granular calls recorded and fused inside the library (deferred execution)" if args.lazy
-                                  else "op-granular" if args.op_granular else "fused"),
-                       "parallelism": f"domain decomposition {nproc_dir[0]}x{nproc_dir[1]}x{nproc_dir[2]}",
-                       # N > 1: did the overlapped exchange path pass its first-use check against the ordered path
-                       # (x3d2_amd/parallel.py, Comm.self_check; None: not exercised, e.g. one rank or host-staged)
-                       "overlap_self_check": getattr(comm, "self_check_result", None),
-                       "overlap_self_check_error": getattr(comm, "self_check_error", None),
-                   # (ms of two 2 ms spins: one on the candidate communication stream + one on the compute stream, both on
-                   # the compute stream) per candidate: equal = the candidate shares the compute stream's hardware queue
-                   # and was passed over (parallel.Comm._pick_stream)
-                   "comm_stream_probe_ms": getattr(comm, "stream_probe", None),
-                       # N > 1: which decomposition ran, and what its one-step validation (and any it replaced) showed
-                       "decomposition": decomp_name if args.case == "tgv" else "slabs",
-                       "decomposition_requested": requested,
-                       "decompositions_tried": tried or None,
-                       "transport": ("gloo, host staged (ranks share a GPU: a dry run)" if share else
-                                     "RCCL %s" % ".".join(str(v) for v in torch.cuda.nccl.version())) if world > 1 or
-                                    dist.is_initialized() else None,
-                       # exchanges of ONE step after the timed region, HIP events on the stream they were posted from:
-                       # sendrecv = halo rows + boundary values of the decomposed direction, alltoall = Poisson transposes
-                       "exchanges_one_step": exchanges,
-                       "overlap_report": overlap_report,
-                       # 000 solve at 512^3 on one rank: transforms ordered z, x, y with the z transforms inside the
-                       # neighbouring z operator pairs (csrc/zfirst.hip); counted pressure corrections of the fused driver
-                       "poisson_z_first": (int(case.solver.n_zfirst) if not args.lazy
-                                           else int(backend.lazy_stats().get("zfirst", 0)))},
-            "dof_substeps_per_s": value * nstage,
-            "roofline": roofline,
-            "kernel_ms": prof,
-        }
-        if args.lazy:
-            out["lazy_stats"] = backend.lazy_stats()
-        return out
+        return line(exchanges, overlap_report, roofline, prof)
 
     out = measure(case, nproc_dir, dims, args.decomp)
 
@@ -809,7 +859,8 @@ def main():
                 "overlap_self_check": o["config"].get("overlap_self_check"),
                 "comm_stream_probe_ms": o["config"].get("comm_stream_probe_ms")}
 
-    if args.case == "tgv" and args.gpus > 1 and requested == "auto" and os.environ.get("X3D_BENCH_ONE_LAYOUT") != "1":
+    if (args.full and args.case == "tgv" and args.gpus > 1 and requested == "auto"
+            and os.environ.get("X3D_BENCH_ONE_LAYOUT") != "1"):
         # N > 1: BOTH layouts in one run -- the validated default (y slabs: one all-to-all pair per solve over all links)
         # and the north star's / BASELINE configs[3]'s 2-D pencil split [1, 2, N/2] (src/decomp/decomp_2decompfft.f90:42-48);
         # `value` is the better of the two, config.decomposition names it, both stay under `decompositions`
@@ -832,7 +883,7 @@ def main():
                 #  same branch: the verdict is all-reduced like the validation's)
                 ok2, o2 = 1.0, None
                 try:
-                    o2 = measure(built[0], built[1], built[2], other)
+                    o2 = measure(built[0], built[1], built[2], other, dump=False)
                 except Exception as e:  # noqa: BLE001
                     ok2 = 0.0
                     layouts[other] = {"nproc_dir": list(built[1]), "value": None, "error": repr(e)[:300]}
@@ -924,7 +975,7 @@ def main():
             t0 = time.perf_counter()
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                                    "--no-cpu-baseline", "--no-other-configs"] + extra, capture_output=True,
+                                    "--full", "--no-cpu-baseline", "--no-other-configs"] + extra, capture_output=True,
                                    text=True, timeout=300)
                 o = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
                 others[key] = brief(o)
@@ -935,9 +986,10 @@ def main():
             except Exception as e:  # noqa: BLE001 -- the headline line must still be printed
                 others[key] = {"value": None, "error": repr(e)[:300]}
             others[key]["seconds_in_all"] = time.perf_counter() - t0
-        # ... and the reference's UNCHANGED solver.f90 through the Fortran shim (fortran/_build/xcompact_hip: built where the
-        # reference tree is mounted, shipped prebuilt like the library), TGV 512^3, 20 steps: its own "Averaged time per step"
-        shim = os.path.join(ROOT, "fortran", "_build", "xcompact_hip")
+        # ... and the reference's UNCHANGED solver.f90 through the Fortran shim (oracle/_ref/shim/xcompact_hip: built where the
+        # reference tree is mounted, shipped prebuilt with the reference binaries), TGV 512^3, 20 steps: its own "Averaged
+        # time per step"
+        shim = os.path.join(ROOT, "oracle", "_ref", "shim", "xcompact_hip")
         if os.path.exists(shim):
             import re
             import tempfile

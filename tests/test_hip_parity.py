@@ -623,14 +623,14 @@ def test_tgv_trace_two_ranks_vs_reference_two_rank_run(tmp_path):
 
 
 def test_unchanged_reference_solver_through_fortran_shim(tmp_path):
-    """fortran/_build/xcompact_hip = the reference's own solver.f90 / cases /
+    """oracle/_ref/shim/xcompact_hip = the reference's own solver.f90 / cases /
     monitoring (compiled from /root/reference in the build container) linked
     with the hip_backend_t shim over the C ABI.  TGV 64^3, RK3, FFT Poisson:
     monitoring.csv must reproduce the reference trace of SURVEY.md 8c."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "xcompact_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "xcompact_hip")
     if not os.path.exists(exe):
         pytest.skip("shim binary not built (needs the reference tree at build time)")
     r = subprocess.run([exe, os.path.join(root, "fortran", "tgv64.x3d")], cwd=tmp_path, capture_output=True,
@@ -650,7 +650,7 @@ def test_reference_transeq_lowmem_through_fortran_shim(tmp_path):
     import re
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "xcompact_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "xcompact_hip")
     if not os.path.exists(exe):
         pytest.skip("shim binary not built (needs the reference tree at build time)")
     rows = {}
@@ -684,7 +684,7 @@ def test_unchanged_reference_solver_through_fortran_shim_on_several_ranks(nranks
     import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "xcompact_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "xcompact_hip")
     mpirun = shutil.which("mpirun") or "/opt/conda/bin/mpirun"
     if not os.path.exists(exe) or not os.path.exists(mpirun):
         pytest.skip("shim binary not built (needs the reference tree at build time) or no mpirun")
@@ -736,7 +736,7 @@ def test_fortran_shim_decomposed_directions_in_one_pass(nranks, inp, tmp_path):
     import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "xcompact_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "xcompact_hip")
     mpirun = shutil.which("mpirun") or "/opt/conda/bin/mpirun"
     if not os.path.exists(exe) or not os.path.exists(mpirun):
         pytest.skip("shim binary not built (needs the reference tree at build time) or no mpirun")
@@ -785,7 +785,7 @@ def test_fortran_shim_y_slabs_take_the_slab_poisson_solver_z_first(tmp_path):
     import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "xcompact_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "xcompact_hip")
     mpirun = shutil.which("mpirun") or "/opt/conda/bin/mpirun"
     if not os.path.exists(exe) or not os.path.exists(mpirun):
         pytest.skip("shim binary not built (needs the reference tree at build time) or no mpirun")
@@ -1975,7 +1975,8 @@ def test_bench_virtual_ranks_line():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--virtual-ranks", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--virtual-ranks", "2", "--steps", "2", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     o = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -2002,7 +2003,8 @@ def test_bench_two_ranks_dry_run_on_a_shared_gpu_carries_every_key_of_the_multi_
     env = dict(os.environ, X3D_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "128"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "128",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -2030,18 +2032,18 @@ def test_bench_two_ranks_dry_run_on_a_shared_gpu_carries_every_key_of_the_multi_
 
 
 def test_bench_line_contract_one_gpu():
-    """`python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with the keys the round driver reads (metric,
-    value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config) plus
-    `roofline` (bound / achieved / peak / unit / frac / traffic of the dominant kernel, HIP-event timed inside the timed
-    region; round 5: the launches of the same kernel that also do the RK stage timed and counted apart) -- here without the
-    CPU baseline, the other configurations and the PMC child runs (their own flags), 3 timed steps"""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line with the keys the round driver reads
+    (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config)
+    plus `roofline` (bound / achieved / peak / unit / frac / traffic of the dominant kernel, HIP-event timed inside the
+    timed region; round 5: the launches of the same kernel that also do the RK stage timed and counted apart) -- here
+    without the CPU baseline, the other configurations and the PMC child runs (their own flags), 3 timed steps"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-other-configs", "--no-live-traffic"], capture_output=True, text=True,
-                       timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-other-configs", "--no-live-traffic"], capture_output=True,
+                       text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -2067,6 +2069,48 @@ def test_bench_line_contract_one_gpu():
     assert 0.5 < ph["frac"] < 0.8
     assert "tdsops_pass_GBs_nominal_op_granular" in rf and "tdsops_pass_GBs_survey_convention" not in rf
     assert 30.0 < o["ms_per_step"] < 60.0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline keys and nothing that needs runs or
+    timers of its own (roofline, kernel_ms, CPU baselines, other configurations); DIR holds u, v, w after the last timed
+    step -- at 256^3 a seeded sample of each field, the same points in every run, within the 64 MB limit -- and they are
+    those of the same steps run here through the solver"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--n", "256", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    o = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in o, k
+    assert o["steps"] == 2 and o["warmup"] == 1 and o["dtype"] == "f64" and o["higher_is_better"] is True
+    assert abs(o["value"] - 256 ** 3 * 2 / (o["ms_per_step"] * 2e-3)) < 1e-6 * o["value"]
+    for k in ("roofline", "kernel_ms", "cpu_baseline", "other_configs", "decompositions"):
+        assert k not in o, k
+    assert o["config"]["exchanges_one_step"] is None and o["config"]["overlap_report"] is None
+    files = sorted(p.name for p in d.iterdir())
+    assert files == ["u.npy", "v.npy", "w.npy"]
+    assert sum((d / f).stat().st_size for f in files) <= 64 * 10 ** 6
+    from x3d2_amd import make_tgv
+    case = make_tgv(256, fused=True, lazy=False)
+    for it, more in ((1, False), (2, True), (3, False)):  # bench.py: the warm-up step, then the timed ones
+        case.step(it, more=more)
+    s = case.solver
+    n = 256 ** 3
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_BYTES // (3 * 8)))
+    for name in ("u", "v", "w"):
+        got = np.load(d / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == idx.shape, (name, got.dtype, got.shape)
+        ref = s.backend.get_field_data(getattr(s, name)).reshape(-1)[idx]
+        assert np.max(np.abs(got - ref)) <= 1e-12 * np.max(np.abs(ref)), name
 
 
 @pytest.mark.parametrize("n,time_intg", [(256, "RK3"), (512, "RK3"), (256, "RK4"), (256, "RK2"), (256, "RK1"), (256, "AB3"),

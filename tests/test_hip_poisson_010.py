@@ -250,13 +250,13 @@ def test_poisson_bc_110_acceptance(n_wave, kind):
 
 @pytest.mark.parametrize("config", ["000", "010", "100", "110"])
 def test_poisson_bc_acceptance_through_the_fortran_shim(config, tmp_path):
-    """fortran/_build/poisson_bc_hip: the reference's mesh / tdsops / poisson_fft_t%base_init (waves_set incl. its
+    """oracle/_ref/shim/poisson_bc_hip: the reference's mesh / tdsops / poisson_fft_t%base_init (waves_set incl. its
     100 branch) and solve_poisson drivers on hip_backend_t, with the cosine checks of its test_poisson_bc.f90
     (which cannot be pointed at a third backend itself): analytic solution to 1e-11"""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "poisson_bc_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "poisson_bc_hip")
     if not os.path.exists(exe):
         pytest.skip("shim binary not built (needs the reference tree at build time)")
     r = subprocess.run([exe, config], cwd=tmp_path, capture_output=True, text=True, timeout=600)
@@ -703,7 +703,7 @@ def _channel_steps(dims, stretching, beta, fused, nsteps, div_bound=1e-6):
 
 
 def test_unchanged_reference_channel_case_through_fortran_shim(tmp_path):
-    """fortran/_build/xcompact_hip: the reference's own channel case (case/channel.f90, solver.f90,
+    """oracle/_ref/shim/xcompact_hip: the reference's own channel case (case/channel.f90, solver.f90,
     poisson_fft.f90 incl. stretching_matrix) on the HIP backend with the 010 FFT Poisson solve --
     a configuration the reference itself only supports on its CUDA backend.  Its monitoring.csv
     must agree with the Python host driver of this package on the same library."""
@@ -711,7 +711,7 @@ def test_unchanged_reference_channel_case_through_fortran_shim(tmp_path):
     import subprocess
     from x3d2_amd import make_channel
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "fortran", "_build", "xcompact_hip")
+    exe = os.path.join(root, "oracle", "_ref", "shim", "xcompact_hip")
     if not os.path.exists(exe):
         pytest.skip("shim binary not built (needs the reference tree at build time)")
     r = subprocess.run([exe, os.path.join(root, "fortran", "channel33.x3d")], cwd=tmp_path, capture_output=True,

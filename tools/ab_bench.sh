@@ -4,9 +4,10 @@ tag=$1; shift
 envs=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done
 shift
-cd $GRAFT_REPO_ROOT
-env "${envs[@]}" python bench.py --no-cpu-baseline --no-other-configs --no-live-traffic "$@" > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err
-python - gpurun_out/ab_$tag.json $tag <<'PY'
+cd "$(dirname "$0")/.."
+out=${OUT:-out}; mkdir -p $out  # (where the lines go: $OUT, default out/ in the repository)
+env "${envs[@]}" python bench.py --full --no-cpu-baseline --no-other-configs --no-live-traffic "$@" > $out/ab_$tag.json 2> $out/ab_$tag.err
+python - $out/ab_$tag.json $tag <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

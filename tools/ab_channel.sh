@@ -1,9 +1,10 @@
 #!/bin/bash
 # usage (GPU box): tools/ab_channel.sh <tag> [ENV=1 ...]  -- one channel bench line (1024 x 257 x 512) under the given switches
 tag=$1; shift
-cd $GRAFT_REPO_ROOT
-env "$@" python bench.py --case channel --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-live-traffic > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err
-python - gpurun_out/ab_$tag.json $tag <<'PY'
+cd "$(dirname "$0")/.."
+out=${OUT:-out}; mkdir -p $out  # (where the lines go: $OUT, default out/ in the repository)
+env "$@" python bench.py --case channel --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-configs --no-live-traffic > $out/ab_$tag.json 2> $out/ab_$tag.err
+python - $out/ab_$tag.json $tag <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

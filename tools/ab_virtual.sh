@@ -1,9 +1,10 @@
 #!/bin/bash
 # usage (GPU box): tools/ab_virtual.sh <tag> [ENV=1 ...]  -- bench.py --virtual-ranks 8 (the y-slab timeline of an 8-rank job on one GPU)
 tag=$1; shift
-cd $GRAFT_REPO_ROOT
-env "$@" python bench.py --virtual-ranks 8 --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-live-traffic > gpurun_out/abv_$tag.json 2> gpurun_out/abv_$tag.err
-python - gpurun_out/abv_$tag.json $tag <<'PY'
+cd "$(dirname "$0")/.."
+out=${OUT:-out}; mkdir -p $out  # (where the lines go: $OUT, default out/ in the repository)
+env "$@" python bench.py --virtual-ranks 8 --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-configs --no-live-traffic > $out/abv_$tag.json 2> $out/abv_$tag.err
+python - $out/abv_$tag.json $tag <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Everything under profiles/r06_* that comes from the CURRENT tree, in one gpurun session:
 #   gpurun -- 'bash tools/round6_artifacts.sh'   then here: python tools/summarize.py r06 r06 r06 && python tools/collect_r06.py
+# (written before bench.py had --full: its bench lines that read the roofline, cpu_baseline, other_configs or the
+#  layouts of N > 1 need that option today)
 rnd=r06
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
