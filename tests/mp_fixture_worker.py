@@ -36,6 +36,10 @@ def battery(name, fused, rank, comm):
     s = Solver(b, mesh, SolverConfig(Re=c["Re"], dt=c["dt"], time_intg=c["time_intg"], poisson_solver_type="CG",
                                      interpl_scheme=c["interpl"], der2nd_scheme=c["der2nd"], fused=fused,
                                      n_species=1, pr_species=[1.0 / 0.37]))
+    if int(g.get("cfg.hyperviscous", [0])[0]):  # (util.synthetic_case(hyperviscous=True))
+        from util import hyperviscous_der2nd
+        for dp in (s.xdirps, s.ydirps, s.zdirps):
+            hyperviscous_der2nd(dp, mesh, b.alloc_tdsops)
     al = b.allocator
     out = {"offset": np.array(mesh.n_offset)}
     for f, k in ((s.u, "in.u"), (s.v, "in.v"), (s.w, "in.w"), (s.species[0], "in.s")):

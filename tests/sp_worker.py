@@ -83,4 +83,46 @@ elif what == "step512":
     np.savez(sys.argv[2], u=fields[0], v=fields[1], w=fields[2])
     row = case.postprocess(1, 1e-3)
     out = {"enstrophy": float(row[1]), "div_max": float(row[2]), "dtype": str(fields[0].dtype), "n_zfirst": int(s.n_zfirst)}
+elif what == "wide":
+    # the wide-stencil kernels (tests/test_hip_wide_stencils.py) on 4-byte reals: every operator and the direction's
+    # transeq against the FP64 dense solve; 'optimised' interpolation, then hyperviscous der2nd
+    from test_hip_wide_stencils import _dense
+    from util import OPNAMES, dense_apply, dense_transeq, hyperviscous_der2nd, relerr
+    from x3d2_amd import Mesh
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.common import DIR_X, VERT, move_data_loc
+    from x3d2_amd.solver import Solver, SolverConfig
+    per, wall = ("periodic",) * 2, ("dirichlet",) * 2
+    for tag, dims, d, bcs in (("x512", (512, 12, 10), 1, [per] * 3), ("x1024", (1024, 12, 10), 1, [per] * 3),
+                              ("y512", (32, 512, 8), 2, [per] * 3), ("z257", (64, 8, 257), 3, [per, per, wall])):
+        for interpl, hyper in (("optimised", False), ("classic", True)):
+            mesh = Mesh(dims, (1, 1, 1), (2.0, 3.0, 2.5), *bcs)
+            s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True, interpl_scheme=interpl))
+            b, al = s.backend, s.backend.allocator
+            dp = (s.xdirps, s.ydirps, s.zdirps)[d - 1]
+            if hyper:
+                hyperviscous_der2nd(dp, mesh, b.alloc_tdsops)
+            dense = _dense(mesh, d, interpl, hyper)
+            rng = np.random.default_rng(d)
+            arrays = [rng.standard_normal((dims[2], dims[1], dims[0])) for _ in range(3)]
+            for f, a in zip((s.u, s.v, s.w), arrays):
+                f.set_data_loc(VERT)
+                b.set_field_data(f, a)
+            worst = {}
+            for op in OPNAMES:
+                t = getattr(dp, op)
+                loc = move_data_loc(VERT, d, 1) if op.endswith("p2v") else VERT
+                src, o = al.get_block(DIR_X, VERT), al.get_block(DIR_X)
+                b.veccopy(src, s.u)
+                src.set_data_loc(loc)
+                b.tds_apply(o, src, t, d)
+                o.set_data_loc(move_data_loc(loc, d, t.move))
+                worst[op] = float(relerr(b.get_field_data(o).astype(np.float64), dense_apply(dense[op], arrays[0], 3 - d)))
+                for f in (src, o):
+                    al.release_block(f)
+            rhs = [al.get_block(DIR_X) for _ in range(3)]
+            b.transeq_dir(d, *rhs, s.u, s.v, s.w, s.nu, dp, accumulate=False)
+            for k, (f, want) in enumerate(zip(rhs, dense_transeq(dense, *arrays, s.nu, 3 - d))):
+                worst["transeq." + "uvw"[k]] = float(relerr(b.get_field_data(f, VERT).astype(np.float64), want))
+            out["%s.%s" % (tag, "hyperviscous" if hyper else interpl)] = worst
 print("SPRESULT " + json.dumps(out))

@@ -150,6 +150,9 @@ def oracle_battery(g, nranks):
                         rank=rank)
         s = orc.Solver(mesh, Re=c["Re"], dt=c["dt"], time_intg=c["time_intg"], poisson="CG", comm=comm,
                        interpl=c["interpl"], der2nd=c["der2nd"])
+        if int(g.get("cfg.hyperviscous", [0])[0]):
+            for dp in (s.xdirps, s.ydirps, s.zdirps):
+                hyperviscous_der2nd(dp, mesh, orc.Tdsops)
         b = s.backend
         out = {}
         for f, k in ((s.u, "in.u"), (s.v, "in.v"), (s.w, "in.w")):
@@ -223,15 +226,20 @@ der2nd_scheme = 'compact6'
 """
 
 
-def synthetic_case(dims, nproc, seed=7):
-    """a fixture-shaped dict (namelist + global inputs) for the operator battery: smooth fields + 10 % noise"""
+def synthetic_case(dims, nproc, seed=7, interpl="classic", hyperviscous=False):
+    """a fixture-shaped dict (namelist + global inputs) for the operator battery: smooth fields + 10 % noise.
+    hyperviscous: "cfg.hyperviscous" = 1, which the battery (tests/mp_fixture_worker.py) and oracle_battery honour by
+    swapping der2nd / der2nd_sym for compact6-hyperviscous ones (hyperviscous_der2nd): the namelist has no c_nu"""
     rng = np.random.default_rng(seed)
     nx, ny, nz = dims
     x = np.arange(nx)[None, None, :] * (2 * np.pi / nx)
     y = np.arange(ny)[None, :, None] * (2 * np.pi / ny)
     z = np.arange(nz)[:, None, None] * (2 * np.pi / nz)
-    g = {"cfg.namelist": np.frombuffer(NML.format(dims=", ".join(map(str, dims)),
-                                                  nproc=", ".join(map(str, nproc))).encode(), dtype=np.uint8)}
+    nml = NML.format(dims=", ".join(map(str, dims)), nproc=", ".join(map(str, nproc)))
+    nml = nml.replace("interpl_scheme = 'classic'", f"interpl_scheme = '{interpl}'")
+    g = {"cfg.namelist": np.frombuffer(nml.encode(), dtype=np.uint8)}
+    if hyperviscous:
+        g["cfg.hyperviscous"] = np.array([1])
     for k, (a, b_, c) in zip(("in.u", "in.v", "in.w", "in.s"), ((1, 2, 1), (2, 1, 3), (1, 1, 2), (3, 2, 1))):
         g[k] = np.sin(a * x + 0.3) * np.cos(b_ * y) * np.cos(c * z + 0.1) + 0.1 * rng.standard_normal((nz, ny, nx))
     return g
@@ -308,3 +316,94 @@ def load_big_steps():
 
 def signature_of(fix, prefix):
     return {k: fix[prefix + "." + k] for k in ("sample", "sum", "sumabs", "sumsq", "wsum", "absmax")}
+
+
+# ---- dense float64 references of the compact operators (uniform grids)
+def dense_operator(n, delta, operation, scheme, bc_s, bc_e, from_to=None, sym=None, c_nu=None, nu0_nu=None):
+    """(A, B) of one compact operator as dense float64 matrices, result = solve(A, B @ u): A the tridiagonal left-hand
+    side before its factorisation (dist_b on the diagonal, dist_sa below, dist_sc above, corners when periodic), B the
+    right-hand side stencils (coeffs_s for rows 0..3, coeffs_e for the last 4 rows of n_rhs, coeffs in between; row j reads
+    input j + m - 4; periodic operators wrap, others drop what falls outside [0, n_rhs)).  A is n x n, B is n x n_rhs.
+    Stretch factors are not applied: uniform grids only.  Valid as a reference of the distributed algorithm (truncated
+    2 x 2 coupling) only where rho^n of the solve is negligible."""
+    from x3d2_amd.tdsops import Tdsops
+
+    class _Raw(Tdsops):
+        def _preprocess_dist(self, b):
+            self.raw = (np.array(b[:self.n_tds]), self.dist_sa[:self.n_tds].copy(), self.dist_sc[:self.n_tds].copy())
+            super()._preprocess_dist(b)
+
+    t = _Raw(n, delta, operation, scheme, bc_s, bc_e, from_to=from_to, sym=sym, c_nu=c_nu, nu0_nu=nu0_nu)
+    diag, sa, sc = t.raw
+    A = np.diag(diag) + np.diag(sa[1:], -1) + np.diag(sc[:-1], 1)
+    if t.periodic:
+        A[0, n - 1] += sa[0]
+        A[n - 1, 0] += sc[n - 1]
+    n_in = t.n_rhs
+    B = np.zeros((n, n_in))
+    for j in range(n):
+        c = t.coeffs_s[j] if j < 4 else (t.coeffs_e[j - (n_in - 4)] if j >= n_in - 4 else t.coeffs)
+        for m in range(9):
+            i = j + m - 4
+            if t.periodic:
+                i %= n_in
+            elif not 0 <= i < n_in:
+                continue
+            B[j, i] += c[m]
+    return A, B
+
+
+def dense_dirps(n_vert, delta, bc_s, bc_e, interpl="classic", der2nd="compact6", c_nu=None, nu0_nu=None):
+    """{operator name: (A, B)} of one direction, with the schemes and end conditions allocate_tdsops gives them (Dirichlet
+    ends -> Neumann for the midpoint operators)"""
+    from x3d2_amd.common import BC_DIRICHLET, BC_NEUMANN, BC_PERIODIC
+    mp_s = BC_NEUMANN if bc_s == BC_DIRICHLET else bc_s
+    mp_e = BC_NEUMANN if bc_e == BC_DIRICHLET else bc_e
+    n_cell = n_vert if bc_s == BC_PERIODIC and bc_e == BC_PERIODIC else n_vert - 1
+    d2 = dict(c_nu=c_nu, nu0_nu=nu0_nu)
+    return {"der1st": dense_operator(n_vert, delta, "first-deriv", "compact6", bc_s, bc_e),
+            "der1st_sym": dense_operator(n_vert, delta, "first-deriv", "compact6", bc_s, bc_e, sym=True),
+            "der2nd": dense_operator(n_vert, delta, "second-deriv", der2nd, bc_s, bc_e, **d2),
+            "der2nd_sym": dense_operator(n_vert, delta, "second-deriv", der2nd, bc_s, bc_e, sym=True, **d2),
+            "stagder_v2p": dense_operator(n_cell, delta, "stag-deriv", "compact6", mp_s, mp_e, from_to="v2p"),
+            "stagder_p2v": dense_operator(n_vert, delta, "stag-deriv", "compact6", mp_s, mp_e, from_to="p2v"),
+            "interpl_v2p": dense_operator(n_cell, delta, "interpolate", interpl, mp_s, mp_e, from_to="v2p"),
+            "interpl_p2v": dense_operator(n_vert, delta, "interpolate", interpl, mp_s, mp_e, from_to="p2v")}
+
+
+def dense_apply(op, a, axis):
+    """solve(A, B @ u) along `axis` of the array a (which holds at least n_rhs points along it)"""
+    A, B = op
+    u = np.moveaxis(np.asarray(a, dtype=np.float64), axis, -1)[..., :B.shape[1]]
+    r = np.linalg.solve(A, B @ u.reshape(-1, B.shape[1]).T).T
+    return np.moveaxis(r.reshape(u.shape[:-1] + (A.shape[0],)), -1, axis)
+
+
+def dense_transeq(ops, u, v, w, nu, axis):
+    """the convection-diffusion terms of one direction (transeq_dist_component: -1/2 (c du/dx + d(c u)/dx) + nu d2u/dx2,
+    c the velocity component along `axis`) for the three components, vertex fields [k, j, i].  The component along the
+    direction: der1st, der2nd and der1st_sym for c c; the others: der1st_sym, der2nd_sym and der1st for c u."""
+    conv = (u, v, w)[2 - axis]
+    out = []
+    for f in (u, v, w):
+        own = f is conv
+        t1, t2, t3 = ("der1st", "der2nd", "der1st_sym") if own else ("der1st_sym", "der2nd_sym", "der1st")
+        out.append(-0.5 * (conv * dense_apply(ops[t1], f, axis) + dense_apply(ops[t3], conv * f, axis))
+                   + nu * dense_apply(ops[t2], f, axis))
+    return out
+
+
+HYPERVISCOUS = dict(c_nu=0.22, nu0_nu=63.0)  # the reference's own test values for compact6-hyperviscous
+
+
+def hyperviscous_der2nd(dirps, mesh, alloc):
+    """replace dirps.der2nd / der2nd_sym by compact6-hyperviscous ones (neither allocate_tdsops passes c_nu), allocated
+    with the arguments allocate_tdsops gives them; alloc = HipBackend.alloc_tdsops (product mesh) or the oracle's
+    Tdsops (oracle mesh)"""
+    d0 = dirps.dir - 1
+    bc_s, bc_e = int(mesh.BCs[d0, 0]), int(mesh.BCs[d0, 1])
+    n = int(mesh.vert_dims[d0])
+    vds2, vd2s = np.asarray(mesh.vert_ds2[d0])[:n], np.asarray(mesh.vert_d2s[d0])[:n]
+    for k, sym in (("der2nd", False), ("der2nd_sym", True)):
+        setattr(dirps, k, alloc(n, float(mesh.d[d0]), "second-deriv", "compact6-hyperviscous", bc_s, bc_e, stretch=vds2,
+                                stretch_correct=vd2s, sym=sym, **HYPERVISCOUS))
