@@ -1081,14 +1081,13 @@ def test_yz_operators_on_512_row_pencils(dims, bc, stretch):
             fo.data_loc = orc.VERT
 
 
-@pytest.mark.parametrize("switch", ["X3D_NO_DIRECT", "X3D_YHALF"])
+@pytest.mark.parametrize("switch", ["X3D_NO_DIRECT"])
 def test_wall_normal_pencils_in_their_other_forms(switch):
-    """The 257-row Dirichlet pencils of the channel case (BASELINE configs[4]) through the forms that are NOT the default:
+    """The 257-row Dirichlet pencils of the channel case (BASELINE configs[4]) through the form that is NOT the default:
     X3D_NO_DIRECT=1 -- the reference's distributed form on the lanes (scan_solve + the reduced 2 x 2 system), what every
-    operator without DIRECT tables still runs; X3D_YHALF=1 -- K3h, two pencils per wave (csrc/ygen.hip).  The default, the
-    DIRECT form (thomas_solve: the plain Thomas recurrences of the tridiagonal system tds.hip recovers from the preprocessed
-    arrays), is what test_yz_operators_on_512_row_pencils runs.  The switches are read once per process: child pytest runs of
-    the 257- and 320-row cases (dims7, dims9, dims12)."""
+    operator without DIRECT tables still runs.  The default, the DIRECT form (thomas_solve: the plain Thomas recurrences of
+    the tridiagonal system tds.hip recovers from the preprocessed arrays), is what test_yz_operators_on_512_row_pencils
+    runs.  The switch is read once per process: child pytest runs of the 257- and 320-row cases (dims7, dims9, dims12)."""
     import subprocess
     import sys
     r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-x", "-q", "-m", "gpu", "-k",
@@ -1920,24 +1919,13 @@ def test_round3_fusion_entry_points_decline_or_fail_loudly(monkeypatch):
         _lib.check(p.backend.lib.x3d_pfft_create_parts(p.backend.h, ctypes.byref(h), _lib.ints(32, 32, 32), 1, 1, 0, 0, 5))
 
 
-@pytest.mark.parametrize("interpl,form", [("classic", "np16"), ("optimised", "np16"), ("aggressive", "np16"), ("classic", "np8"),
-                                          ("optimised", "np8"), ("aggressive", "np8")])
+@pytest.mark.parametrize("interpl,form", [("classic", "np16"), ("optimised", "np16"), ("aggressive", "np16")])
 def test_z_transforming_pair_kernels_against_pair_kernel_plus_stand_alone_transform(interpl, form):
     """the z-transforming operator pairs by themselves, 512^3: mode 0 (pair -> spectrum) followed by the stand-alone
     inverse z transform == 512 x the plain pair's result; the stand-alone forward transform followed by mode 1
     (spectrum -> pair) == 512 x the plain pair on the field.  'optimised' interpolation has a 7-point right-hand side: the
-    kernels' wide-stencil (NARROW = false) instantiations; 'aggressive' (rho^64 = 2e-6) has no compressed lane tables, so
-    np8 declines and the np16 form serves it.  np16 (the default): k_ytile_tds_pair<8, MODE, .., ZF>; np8
-    (round 6: built, parity-green, measured slower -- off unless X3D_ZF_NP8=1, read once per process: a child pytest):
-    k_zfpair8 -- 8-pencil tiles, two workgroups per CU, compressed lane tables (csrc/zfpair8.hip)"""
-    if form == "np8" and os.environ.get("X3D_ZF_NP8") != "1":
-        import subprocess
-        import sys
-        r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-x", "-q", "-m", "gpu", "-k",
-                            "z_transforming_pair_kernels and %s-np8" % interpl], env=dict(os.environ, X3D_ZF_NP8="1"),
-                           capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:]
-        return
+    kernels' wide-stencil (NARROW = false) instantiations.  np16: k_ytile_tds_pair<8, MODE, .., ZF>, 16-pencil tiles (the
+    8-pencil form, measured slower, was removed)"""
     import torch
     from x3d2_amd import Mesh
     from x3d2_amd.backend import HipBackend

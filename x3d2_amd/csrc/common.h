@@ -84,25 +84,17 @@ __device__ __forceinline__ void wave_lds_fence()
 // stores (5.6 with plain ones: profiles/r04_copy_ceiling.txt); every field row of the derivative kernels is read once
 // and written once per launch, so their global accesses carry the hint.  The builtin has no overload for HIP's real2_t
 // struct -- through an ext_vector_type the access stays ONE global_load_dwordx4 ... nt (two 8-byte builtins do not
-// always fuse back).  -DX3D_NO_NT: plain accesses (A/B builds).
+// always fuse back).
 typedef real_t x3d_d2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ real2_t ldg_stream(const real2_t *p)
 {
-#ifndef X3D_NO_NT
     const x3d_d2v v = __builtin_nontemporal_load(reinterpret_cast<const x3d_d2v *>(p));
     return make_real2(v.x, v.y);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ void stg_stream(real2_t *p, real2_t v)
 {
-#ifndef X3D_NO_NT
     const x3d_d2v w = {v.x, v.y};
     __builtin_nontemporal_store(w, reinterpret_cast<x3d_d2v *>(p));
-#else
-    *p = v;
-#endif
 }
 
 // Store acknowledgements and loop-carried prefetches (round 4).  On gfx950 loads and stores share ONE in-order counter
@@ -115,7 +107,6 @@ __device__ __forceinline__ void stg_stream(real2_t *p, real2_t v)
 // in the prologue as the loop body issues operations behind its prefetch makes both entries look alike: the wait
 // becomes vmcnt(n) and the stores drain behind the next iteration's work.  Performance only: the values land in a
 // sink nobody reads.
-#ifndef X3D_NO_VMCNT_PAD
 static __device__ __attribute__((used)) float g_vmcnt_sink[32 * 1024];
 template <int N>
 __device__ __forceinline__ void vmcnt_pad_stores()
@@ -123,9 +114,6 @@ __device__ __forceinline__ void vmcnt_pad_stores()
 #pragma unroll
     for (int k = 0; k < N; k++) __builtin_nontemporal_store(0.0f, &g_vmcnt_sink[k * 1024 + (threadIdx.x & 1023)]);
 }
-#else
-template <int N> __device__ __forceinline__ void vmcnt_pad_stores() {}
-#endif
 
 // Pencil enumeration for one direction of the Cartesian-pitched block:
 // pencil p -> base = (p % dim0) * s0 + (p / dim0) * s1, rows advance by rs.
@@ -357,7 +345,7 @@ struct x3d_tdsops {
                                  //    operators whose two ends are neighbour ranks (BC_HALO: the same rows)
     TdsTab tabc;                 // circ_open_ok: the strip corrections of the circulant HALO form in the strip kernels' table layout
     int halo_ws_c, halo_we_c;    // ... and the rows they reach (as halo_ws / halo_we)
-    const real_t *td5, *td8h;    // DIRECT lane tables (tds.hip, ygen.hip): 5 rows per lane; 8 rows per lane of a half-wave + row 257
+    const real_t *td5;           // DIRECT lane tables (tds.hip, ygen.hip): 5 rows per lane
     int narrow_all;              // 1: no stencil of the operator (bulk, start rows, end rows) reaches beyond 2 rows
     int uniform;                 // 1: stretch == 1 and stretch_correct == 0 on every row (a uniform grid): kernels may skip
                                  //    the ST / STC lane-table reads and their multiplications (x * 1.0, + nu * x * 0.0)

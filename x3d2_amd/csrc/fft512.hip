@@ -407,20 +407,11 @@ int x3d_fft512_run_zh(x3d_backend *b, real2_t *c, long px, int kz0, int nkz, con
     // the planes kz0 .. kz0 + nkz - 1 (the kernel numbers its rows' other index from 0)
     c += (long)kz0 * ny * px;
     const Spec000 sp{nullptr, ax, bx, ay, by, az + kz0, bz + kz0, nx, ny, nz, rwZ + (size_t)kz0 * 512 * 512};
-    static int np16 = -1;
-    if (np16 < 0) { const char *e = getenv("X3D_ZFIRST_Y16"); np16 = (e && e[0] == '1') ? 1 : 0; }
     ProfScope ps(b, X3D_K_SPECTRAL, 1);
-    if (np16) {
-        const int lds = sizeof(real2_t) * (16 * FP + 256);
-        X3D_LDS_OPTIN(b, (k_fft512<2, 16, true>));
-        hipLaunchKernelGGL((k_fft512<2, 16, true>), dim3(512 / 16, nkz), dim3(1024), lds, b->stream, c, g_tw, px,
-                           (long)ny * px, 512, sp, nullptr, 1, 1);
-    } else {
-        const int lds = sizeof(real2_t) * (8 * FP + 256);
-        X3D_LDS_OPTIN(b, (k_fft512<2, 8, true>));
-        hipLaunchKernelGGL((k_fft512<2, 8, true>), dim3(512 / 8, nkz), dim3(512), lds, b->stream, c, g_tw, px,
-                           (long)ny * px, 512, sp, nullptr, 1, 1);
-    }
+    const int lds = sizeof(real2_t) * (8 * FP + 256);
+    X3D_LDS_OPTIN(b, (k_fft512<2, 8, true>));
+    hipLaunchKernelGGL((k_fft512<2, 8, true>), dim3(512 / 8, nkz), dim3(512), lds, b->stream, c, g_tw, px,
+                       (long)ny * px, 512, sp, nullptr, 1, 1);
     X3D_HIP(hipGetLastError());
     return 0;
 }
@@ -469,19 +460,14 @@ int x3d_fft512_run_x(x3d_backend *b, real2_t *c, int nxs, int ny, int nz, int ax
         const real_t *ax = ab, *bx = ax + nx, *ay = bx + nx, *by = ay + ny, *az = by + ny, *bz = az + nz;
         sp = Spec000{waves, ax, bx, ay, by, az, bz, nx, ny, nz, g_rwT};
     }
-    static int wide = -1;  // rows of 256 B (16 modes, one 16-wave workgroup per CU) instead of 128 B
-    if (wide < 0) {
-        const char *e = getenv("X3D_FFT512_WIDE");
-        wide = e ? atoi(e) : 1;  // measured: y pass 0.53 vs 0.58 ms with 16 modes, z pass 0.90 vs 0.96 with 8
-    }
-    const bool w16 = (wide & axis) != 0;  // bit 0: y pass, bit 1: z pass
+    // the y pass on rows of 256 B (16 modes, one 16-wave workgroup per CU), the z pass on rows of 128 B (8 modes) --
+    // measured: y pass 0.53 vs 0.58 ms with 16 modes, z pass 0.90 vs 0.96 with 8
+    const bool w16 = axis == 1;
     ProfScope ps(b, mode == 2 ? X3D_K_SPECTRAL : X3D_K_FFT, axis);
-#define GO(M_)                                                                                             \
-    (w16 ? launch512<M_, 16>(b, c, stride_axis, stride_other, nxs, nother, sp, xbuf, ys, ysc)              \
-         : launch512<M_, 8>(b, c, stride_axis, stride_other, nxs, nother, sp, xbuf, ys, ysc))
-    if (mode == 0) return GO(0);
-    if (mode == 1) return GO(1);
-    return GO(2);
+#define GO(M_, NP_) launch512<M_, NP_>(b, c, stride_axis, stride_other, nxs, nother, sp, xbuf, ys, ysc)
+    if (mode == 0) return w16 ? GO(0, 16) : GO(0, 8);
+    if (mode == 1) return w16 ? GO(1, 16) : GO(1, 8);
+    return GO(2, 8);
 #undef GO
 }
 

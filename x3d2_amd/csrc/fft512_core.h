@@ -96,10 +96,9 @@ __device__ __forceinline__ void fft512_wave(real2_t (&a)[8], real2_t *__restrict
 }
 
 
-// ---- 256-point complex FFT of one pencil per wave, FOUR points per lane (round 4 experiment, -DZF_16WAVES, measured
-// slower and off by default -- profiles/r04_zf16_waves.txt: the z transforms on the tile of the
-// z operator pairs give every one of the 16 waves ONE real pencil -- 512 reals as 256 complex numbers -- instead of two
-// real pencils to 8 of them).  in / out a[k] = point l + 64 k; pen = this wave's LDS region (FP256 real2_t).
+// ---- 256-point complex FFT of one pencil per wave, FOUR points per lane (round 4; its first use, the z transforms of the
+// z operator pairs on 16 waves, measured slower and was removed -- profiles/r04_zf16_waves.txt).  in / out a[k] = point
+// l + 64 k; pen = this wave's LDS region (FP256 real2_t).
 // 256 = 4 x 4 x 4 x 4, decimation in frequency: f = f1 + 4 f2 + 16 f3 + 64 f4; every stage is a 4-point DFT in
 // registers, the three exchanges go through the wave's own region (no block barrier: a wave's LDS operations execute in
 // order).  Unnormalised, S = -1 forward / +1 backward like fft512_wave.

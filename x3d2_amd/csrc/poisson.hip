@@ -604,13 +604,10 @@ extern "C" int x3d_poisson_solve_010_rows(x3d_poisson *p, real_t *f)
         bool done = false;
         // X3D_Y010_FORM: "split" = k_y010<0> ; k_penta_solve x 2 ; k_y010<1>.  "staged" = the forward sweeps on the
         // tile of the first kernel, the backward sweeps on the tile of the second, the factored operator staged in LDS
-        // (k_y010<3> ; k_y010<4>).  "fused" = everything in k_y010<2>, the operator streamed by the chains (slow).
+        // (k_y010<3> ; k_y010<4>)
         const char *ef = getenv("X3D_Y010_FORM");
-        const int form = !ef || !ef[0] ? Y010_DEFAULT_FORM : (ef[0] == 'f' ? 2 : (ef[0] == 's' && ef[1] == 't' ? 1 : 0));
-        if (form == 2) {
-            ProfScope ps(b, X3D_K_SPECTRAL);
-            if (int rc = x3d_y010_run(b, p->c, p->nxs, p->nx, p->ny, p->nz, 2, p->ab, p->sym, p->lu, &done)) return rc;
-        } else if (form == 1) {
+        const int form = !ef || !ef[0] ? Y010_DEFAULT_FORM : (ef[0] == 's' && ef[1] == 't' ? 1 : 0);
+        if (form == 1) {
             {
                 ProfScope ps(b, X3D_K_SPECTRAL);
                 if (int rc = x3d_y010_run(b, p->c, p->nxs, p->nx, p->ny, p->nz, 3, p->ab, p->sym, p->lu, &done)) return rc;

@@ -173,7 +173,7 @@ extern "C" int x3d_tdsops_create(x3d_backend *b, x3d_tdsops **out, int n_tds, in
     // compressed form of the row entries (xscan_core.h, LTC_*): lanes 0..7 | one value for lanes 8..55 | lanes
     // 56..63 -- only where those middle lanes really are bitwise equal (periodic-type operators on a uniform grid)
     size_t tlc_off = 0;
-    if (Q == 16 || Q == 8) {  // (Q = 8, round 6: the 8-pencil z-transforming pairs, zfpair8.hip)
+    if (Q == 16) {
         const real_t *tl = &img[tl_off];
         bool ok = true;
         auto row_entry = [&](int k) { return k < 8 * Q ? k : 8 * Q + 12 + (k - 8 * Q); };  // k = 0 .. 9Q-1
@@ -213,7 +213,7 @@ extern "C" int x3d_tdsops_create(x3d_backend *b, x3d_tdsops **out, int n_tds, in
     // du_1 / X_n broadcasts, no row selects): the matrix is recovered from the preprocessed arrays (the inverse of
     // preprocess_dist, src/tdsops.f90:874-931), factored here, and the result is checked on the host against the
     // reference's own sweeps before the tables are offered.
-    size_t td5_off = 0, td8h_off = 0;
+    size_t td5_off = 0;
     {
         bool direct = !periodic && dist_sa[0] == 0.0 && dist_sc[n - 1] == 0.0 && n >= 8;
         std::vector<real_t> ma(n + 2, 0.0), mb(n + 2, 0.0), mc(n + 2, 0.0), TF(L, 0.0), TFA(L, 0.0), TH(L, 0.0);
@@ -269,10 +269,10 @@ extern "C" int x3d_tdsops_create(x3d_backend *b, x3d_tdsops **out, int n_tds, in
             }
         }
         t->direct = direct ? 1 : 0;
-        // [7 Q + 16][64]: F FA PF H QB ST | 6 + 6 scan multipliers | XR (4) | STC; LP lanes per pencil (32: two pencils per
-        // wave, the tables of lanes 32..63 repeat lanes 0..31); XR: row LP Q + 1 exists and is carried by the pencil's last
-        // lane (257 rows = 32 x 8 + 1): its F, FA, ST, STC, every lane the same
-        auto build_direct = [&](const int Q, const int LP, std::vector<real_t> &out) {
+        // [7 Q + 16][64]: F FA PF H QB ST | 6 + 6 scan multipliers | XR (4) | STC; XR: row 64 Q + 1 exists and is carried by
+        // the pencil's last lane: its F, FA, ST, STC, every lane the same
+        auto build_direct = [&](const int Q, std::vector<real_t> &out) {
+            constexpr int LP = 64;
             const bool XR = n == LP * Q + 1;
             const int NE = 7 * Q + 16;
             out.assign((size_t)NE * 64, 0.0);
@@ -320,9 +320,9 @@ extern "C" int x3d_tdsops_create(x3d_backend *b, x3d_tdsops **out, int n_tds, in
                 for (int i = l; i <= 31; i++) d32 *= HL[i];
                 const int row = l >> 4;
                 E(6 * Q + 4, l) = (row == 1 || row == 3) ? c15 : 0.0;
-                E(6 * Q + 5, l) = (LP == 64 && row >= 2) ? c31 : 0.0;
+                E(6 * Q + 5, l) = row >= 2 ? c31 : 0.0;
                 E(6 * Q + 6 + 4, l) = (row == 0 || row == 2) ? d16 : 0.0;
-                E(6 * Q + 6 + 5, l) = (LP == 64 && row < 2) ? d32 : 0.0;
+                E(6 * Q + 6 + 5, l) = row < 2 ? d32 : 0.0;
             }
             if (XR) {
                 for (int l = 0; l < LP; l++) {
@@ -332,20 +332,11 @@ extern "C" int x3d_tdsops_create(x3d_backend *b, x3d_tdsops **out, int n_tds, in
                     E(6 * Q + 12 + 3, l) = Stc[n];
                 }
             }
-            if (LP == 32)
-                for (int e = 0; e < NE; e++)
-                    for (int l = 0; l < 32; l++) E(e, 32 + l) = E(e, l);
         };
         if (direct && nr > 256 && nr <= 320) {
             std::vector<real_t> tlv;
-            build_direct(5, 64, tlv);
+            build_direct(5, tlv);
             td5_off = img.size();
-            img.insert(img.end(), tlv.begin(), tlv.end());
-        }
-        if (direct && nr == 257) {  // (n = 257: with the extra row; n = 256: a v2p operator, 32 x 8 rows)
-            std::vector<real_t> tlv;
-            build_direct(8, 32, tlv);
-            td8h_off = img.size();
             img.insert(img.end(), tlv.begin(), tlv.end());
         }
     }
@@ -445,7 +436,6 @@ extern "C" int x3d_tdsops_create(x3d_backend *b, x3d_tdsops **out, int n_tds, in
     X3D_HIP(hipMemcpy(t->dev, img.data(), sizeof(real_t) * img.size(), hipMemcpyHostToDevice));
     t->tl5 = tl5_off ? t->dev + tl5_off : nullptr;
     t->td5 = td5_off ? t->dev + td5_off : nullptr;
-    t->td8h = td8h_off ? t->dev + td8h_off : nullptr;
     TdsTab &tb = t->tab;
     tb.n_tds = n; tb.n_rhs = nr; tb.chunk = chunk;
     tb.RF = t->dev; tb.RB = t->dev + (size_t)4 * L;

@@ -86,17 +86,6 @@ static bool use_via_x()
     return mode == 1;
 }
 
-static int via_slabs(int nC)
-{
-    static int n = -1;
-    if (n < 0) {
-        const char *e = getenv("X3D_VIA_SLABS");
-        n = e ? atoi(e) : 1;
-        if (n < 1) n = 1;
-    }
-    return n > nC ? nC : n;
-}
-
 struct ViaGeom {
     int nA, nB, nC;        // forward transpose: A = x (contiguous in the block), B = the pencil direction, C = the other
     long f_dA, f_dC, f_sB, f_sC;
@@ -122,24 +111,20 @@ static ViaGeom via_geom(const x3d_backend *b, int dir)
     return g;
 }
 
-// (c0, nc): the slab of C planes to move
-static int to_pencils(x3d_backend *b, const ViaGeom &g, real_t *T, const real_t *f, int c0, int nc)
+static int to_pencils(x3d_backend *b, const ViaGeom &g, real_t *T, const real_t *f)
 {
-    dim3 grid((g.nA + 63) / 64, (g.nB + 63) / 64, nc);
-    hipLaunchKernelGGL((k_transpose64<false, false>), grid, dim3(256), 0, b->stream, T + c0 * g.f_dC, f + c0 * g.f_sC,
-                       g.nA, g.nB, g.f_dA, g.f_dC, g.f_sB, g.f_sC);
+    dim3 grid((g.nA + 63) / 64, (g.nB + 63) / 64, g.nC);
+    hipLaunchKernelGGL((k_transpose64<false, false>), grid, dim3(256), 0, b->stream, T, f, g.nA, g.nB, g.f_dA, g.f_dC, g.f_sB,
+                       g.f_sC);
     X3D_HIP(hipGetLastError());
     return 0;
 }
 
-static int from_pencils(x3d_backend *b, int dir, const ViaGeom &g, real_t *r, const real_t *T, int acc, int c0,
-                        int nc)
+static int from_pencils(x3d_backend *b, int dir, const ViaGeom &g, real_t *r, const real_t *T, int acc)
 {
     ProfScope ps(b, X3D_K_TRANSEQ_BWD, dir);
     // inverse: A' = the pencil direction (contiguous in T), B' = x
-    dim3 grid((g.nB + 63) / 64, (g.nA + 63) / 64, nc);
-    r += c0 * g.f_sC;
-    T += c0 * g.f_dC;
+    dim3 grid((g.nB + 63) / 64, (g.nA + 63) / 64, g.nC);
     if (acc)
         hipLaunchKernelGGL((k_transpose64<true, true>), grid, dim3(256), 0, b->stream, r, T, g.nB, g.nA, g.f_sB, g.f_sC, g.f_dA,
                            g.f_dC);
@@ -180,32 +165,23 @@ int x3d_transeq_via_x(x3d_backend *b, int dir, real_t *const r[3], const real_t 
         }
     }
     real_t *T0 = b->scratch[0], *T1 = b->scratch[1], *tmp = b->scratch[2];
-    // slabs of C planes: the transposed copies and the scan kernel's output of one slab are produced and
-    // consumed back to back, so that most of their re-reads hit the 256 MB Infinity Cache
-    const int nslab = via_slabs(g.nC);
-    for (int sl = 0; sl < nslab; sl++) {
-        const int c0 = (int)((long)g.nC * sl / nslab), nc = (int)((long)g.nC * (sl + 1) / nslab) - c0;
-        const long off = c0 * g.f_dC;  // pencils c0 * nA ... of the transposed copies
-        const int np = nc * g.nA;
-        for (int c = 0; c < 3; c++) {
-            bool ok = false;
-            real_t *T = c == 0 ? T0 : T1;
-            // profiler: transpose + scan kernel = the component's "forward" launch, the accumulating
-            // inverse transpose its "backward" launch (bench.py prices a component as fwd + bwd)
-            {
-                ProfScope ps(b, X3D_K_TRANSEQ_FWD, dir);
-                if (int rc = to_pencils(b, g, T, f[c], c0, nc)) return rc;
-                if (int rc = x3d_xscan_transeq_np(b, tmp + off, T + off, T0 + off, nu, c == 0 ? der1st : der1st_sym,
-                                                  c == 0 ? der1st_sym : der1st, c == 0 ? der2nd : der2nd_sym, 0, np,
-                                                  g.pitch, -1, &ok))
-                    return rc;
-            }
-            if (!ok) {
-                X3D_REQUIRE(sl == 0 && c == 0, "x3d_transeq_via_x: scan kernel refused component %d", c);
-                return 0;  // nothing written to r yet
-            }
-            if (int rc = from_pencils(b, dir, g, r[c], tmp, acc, c0, nc)) return rc;
+    for (int c = 0; c < 3; c++) {
+        bool ok = false;
+        real_t *T = c == 0 ? T0 : T1;
+        // profiler: transpose + scan kernel = the component's "forward" launch, the accumulating
+        // inverse transpose its "backward" launch (bench.py prices a component as fwd + bwd)
+        {
+            ProfScope ps(b, X3D_K_TRANSEQ_FWD, dir);
+            if (int rc = to_pencils(b, g, T, f[c])) return rc;
+            if (int rc = x3d_xscan_transeq_np(b, tmp, T, T0, nu, c == 0 ? der1st : der1st_sym, c == 0 ? der1st_sym : der1st,
+                                              c == 0 ? der2nd : der2nd_sym, 0, g.np, g.pitch, -1, &ok))
+                return rc;
         }
+        if (!ok) {
+            X3D_REQUIRE(c == 0, "x3d_transeq_via_x: scan kernel refused component %d", c);
+            return 0;  // nothing written to r yet
+        }
+        if (int rc = from_pencils(b, dir, g, r[c], tmp, acc)) return rc;
     }
     *done = true;
     return 0;
@@ -326,7 +302,7 @@ extern "C" int x3d_transeq_defer(x3d_backend *b, int dir, real_t *pu, real_t *pv
         real_t *T = c == 0 ? T0 : T1;
         bool ok = false;
         ProfScope ps(b, X3D_K_TRANSEQ_FWD, dir);
-        if (int rc = to_pencils(b, g, T, fld[m], 0, g.nC)) return rc;
+        if (int rc = to_pencils(b, g, T, fld[m])) return rc;
         if (int rc = x3d_xscan_transeq_np(b, pend[m], T, T0, nu, c == 0 ? der1st : der1st_sym,
                                           c == 0 ? der1st_sym : der1st, c == 0 ? der2nd : der2nd_sym, 0, g.np, g.pitch,
                                           -1, &ok))
@@ -348,7 +324,7 @@ extern "C" int x3d_pending_flush(x3d_backend *b, int dir, real_t *r, const real_
     X3D_LAZY_EAGER(b);
     X3D_REQUIRE(b && r && pend, "x3d_pending_flush: null argument");
     X3D_REQUIRE(dir == X3D_DIR_Y || dir == X3D_DIR_Z, "x3d_pending_flush: dir must be Y or Z");
-    return from_pencils(b, dir, via_geom(b, dir), r, pend, 1, 0, via_geom(b, dir).nC);
+    return from_pencils(b, dir, via_geom(b, dir), r, pend, 1);
 }
 
 extern "C" int x3d_lincomb_pending(x3d_backend *b, int dir, real_t *y, const real_t *base, int nterm,

@@ -21,10 +21,7 @@ int x3d_generic_transeq_local(x3d_backend *b, int dir, real_t *rhs, const real_t
                               int acc);
 int npmax_of(const x3d_backend *b);
 
-#ifndef X3D_XTW
-#define X3D_XTW 16   // tile width (columns): 128 B contiguous per row per fetch (32 costs too many VGPRs)
-#endif
-#define TW X3D_XTW
+#define TW 16        // tile width (columns): 128 B contiguous per row per fetch (32 costs too many VGPRs)
 #define TP 65        // LDS pitch in doubles
 #define TILE (TW * TP)
 #define TLD (TW / 2) // 16-byte loads per lane per tile: 64 rows * TW cols / (64 lanes * 2)

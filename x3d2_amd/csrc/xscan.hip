@@ -16,27 +16,11 @@
 // Row tables live in LDS as [entry][lane] (conflict-free ds_read_b64).
 #include "common.h"
 
-// FAST transeq kernel: one workgroup per CU (129 KB of lane tables).  Measured: 12 waves with next-pencil
-// prefetch (163 VGPRs) 0.96 ms per component, 16 waves without it (123 VGPRs) 0.90 ms.
-#ifndef YT_NOPREF
-#define YT_PREF 1  // K3y: next tile's u rows prefetched into registers (same-box A/B: 1.05 -> 0.92 ms per component)
-#endif
-#ifndef XS_TQ_THREADS
-#define XS_TQ_THREADS 1024
-#ifndef XS_PREF
-#define XS_NOPREF 1
-#endif
-#endif
-
-// nontemporal loads / stores of the rhs rows in the three-in-one tile kernel (-DYT_NO_NT: plain): same-box A/B
-// k_ytile_transeq3 z 2.21 -> 2.16 ms, y 2.24 -> 2.23; full step at 512^3 within noise, at 256^3 5.52 -> 5.44 ms
-#ifndef YT_NO_NT
-#define YT_NT 1
-#endif
-
-#ifndef XSCAN_EXP
-#define XSCAN_EXP 0  // timing experiments only (1: no stores, 2: no loads, 3: no scans)
-#endif
+// FAST transeq kernel: one 16-wave workgroup per CU (129 KB of lane tables), no next-pencil prefetch.  Measured: 12 waves
+// with the prefetch (163 VGPRs) 0.96 ms per component, 16 waves without it (123 VGPRs) 0.90 ms.
+// K3y: the next tile's u rows are prefetched into registers (same-box A/B: 1.05 -> 0.92 ms per component).
+// Nontemporal loads / stores of the rhs rows in the three-in-one tile kernel: same-box A/B k_ytile_transeq3 z 2.21 -> 2.16
+// ms, y 2.24 -> 2.23; full step at 512^3 within noise, at 256^3 5.52 -> 5.44 ms
 
 int npmax_of(const x3d_backend *b);
 
@@ -80,11 +64,7 @@ __device__ __forceinline__ void store_rows_q8(real_t *__restrict__ orow, int lan
         v0.x = a0; v0.y = a1; v1.x = d0; v1.y = d1; v2.x = c0; v2.y = c1; v3.x = b0; v3.y = b1;
     }
     // (plain stores: an instruction writes whole 64-byte sectors but only half of each 128-byte line)
-#ifdef XS_NT_STORES  // experiment: nontemporal stores only (the loads stay cached)
-    stg_stream(o2, v0); stg_stream(o2 + 4, v1); stg_stream(o2 + 8, v2); stg_stream(o2 + 12, v3);
-#else
     o2[0] = v0; o2[4] = v1; o2[8] = v2; o2[12] = v3;
-#endif
 }
 
 // Q = 4: a lane owns 32 B, a pair of lanes one 64-byte sector: 2 x 2 transpose of the 16-byte pairs
@@ -166,11 +146,7 @@ __global__ void __launch_bounds__(512) k_xscan_tds(real_t *__restrict__ du, cons
         real_t w[Q + 8], X[Q], du1, xn;
         if (FAST) {
             window_from_body<Q>(w, nb, lane);
-#if XSCAN_EXP == 2
-            for (int q = 0; q < Q; q++) nb[q] = nb[q] * 1.0000001 + lane;
-#else
             if (p + nwaves < np) load_body<Q>(nb, u + (long)(p + nwaves) * pitch, lane);
-#endif
         } else if (exact) load_window_exact<Q>(w, row, lane, nr);
         else load_window<Q>(w, row, first, nr, n_wrap, interior);
         real_t *__restrict__ orow = du + (long)p * pitch;
@@ -195,9 +171,6 @@ __global__ void __launch_bounds__(512) k_xscan_tds(real_t *__restrict__ du, cons
             }
         }
         }  // (!CIRC)
-#if XSCAN_EXP == 1
-        if (r[0] != 12345.678) continue;
-#endif
         if constexpr (FAST != 0) {
             if constexpr (Q == 8) store_rows_q8<ACC>(orow, lane, r, scale);
             else store_rows_q4<ACC>(orow, lane, r, scale);
@@ -284,7 +257,7 @@ __global__ void __launch_bounds__(512) k_xscan_tds_lin(real_t *__restrict__ du, 
 
 // ---------------------------------------------------------------- transeq component
 template <int Q, bool SAME, bool ACC, int FAST>
-__global__ void __launch_bounds__(FAST ? XS_TQ_THREADS : 512)
+__global__ void __launch_bounds__(FAST ? 1024 : 512)
     k_xscan_transeq(real_t *__restrict__ rhs, const real_t *__restrict__ u, const real_t *__restrict__ cv, XOp t1,
                     XOp t2, XOp t3, int np, long pitch, real_t nu)
 {
@@ -311,12 +284,6 @@ __global__ void __launch_bounds__(FAST ? XS_TQ_THREADS : 512)
     const real_t *__restrict__ l1 = lt, *__restrict__ l2 = lt + LN, *__restrict__ l3 = lt + 2 * LN;
     const int p0 = blockIdx.x * (blockDim.x >> 6) + wave;
     real_t nbu[Q], nbc[Q];  // FAST: next pencil's rows of u and conv, in flight during the solve
-#ifndef XS_NOPREF
-    if (FAST && p0 < np) {
-        load_body<Q>(nbu, u + (long)p0 * pitch, lane);
-        if (!SAME) load_body<Q>(nbc, cv + (long)p0 * pitch, lane);
-    }
-#endif
     for (int p = p0; p < np; p += nwaves) {
         const real_t *__restrict__ ru = u + (long)p * pitch;
         const real_t *__restrict__ rc = cv + (long)p * pitch;
@@ -324,10 +291,8 @@ __global__ void __launch_bounds__(FAST ? XS_TQ_THREADS : 512)
         real_t wu[Q + 8], wp[Q + 8], vq[Q];
         const bool exact = FAST || n == 64 * Q;
         if (FAST) {
-#ifdef XS_NOPREF
             load_body<Q>(nbu, u + (long)p * pitch, lane);
             if (!SAME) load_body<Q>(nbc, cv + (long)p * pitch, lane);
-#endif
             window_from_body<Q>(wu, nbu, lane);
             if (!SAME) {
                 window_from_body<Q>(wp, nbc, lane);
@@ -337,12 +302,6 @@ __global__ void __launch_bounds__(FAST ? XS_TQ_THREADS : 512)
 #pragma unroll
                 for (int q = 0; q < Q; q++) vq[q] = nbu[q];
             }
-#ifndef XS_NOPREF
-            if (p + nwaves < np) {
-                load_body<Q>(nbu, u + (long)(p + nwaves) * pitch, lane);
-                if (!SAME) load_body<Q>(nbc, cv + (long)(p + nwaves) * pitch, lane);
-            }
-#endif
 #pragma unroll
             for (int m = 0; m < Q + 8; m++) wp[m] = SAME ? wu[m] * wu[m] : wu[m] * wp[m];
         } else {
@@ -754,10 +713,8 @@ __global__ void __launch_bounds__(1024)
         }
     };
     __syncthreads();
-#ifdef YT_PREF
     real2_t nxt[NI];  // next tile's u rows, in flight during the solve
     if ((int)blockIdx.x < ntiles) gload(nxt, u + (long)(blockIdx.x / ntx) * pplane + (long)(blockIdx.x % ntx) * 16);
-#endif
     for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
         const long off = (long)(tl / ntx) * pplane + (long)(tl % ntx) * 16;
         asm volatile("" : "+v"(lane));  // keep the lane-table reads inside the loop
@@ -765,12 +722,8 @@ __global__ void __launch_bounds__(1024)
         {
             real_t b[Q];
             real2_t gu[NI], gc[NI];
-#ifdef YT_PREF
 #pragma unroll
             for (int i = 0; i < NI; i++) gu[i] = nxt[i];
-#else
-            gload(gu, u + off);  // both fields in flight at once: one exposed memory latency per tile, not two
-#endif
             if (!SAME) gload(gc, cv + off);
             to_tile(gu);
             __syncthreads();
@@ -789,12 +742,10 @@ __global__ void __launch_bounds__(1024)
             for (int m = 0; m < Q + 8; m++) wp[m] = SAME ? wu[m] * wu[m] : wu[m] * wp[m];
         }
         // (no barrier here: until the store phase a wave only rewrites its own pencil's region of the tile)
-#ifdef YT_PREF
         {
             const int tn = tl + gridDim.x;
             if (tn < ntiles) gload(nxt, u + (long)(tn / ntx) * pplane + (long)(tn % ntx) * 16);
         }
-#endif
         auto solve_subs = [&](const real_t (&w)[Q + 8], real_t (&T)[Q], const real_t *__restrict__ l, const XOp &t) {
             real_t a, b;
             scan_solve<Q, true, (FAST == 2)>(w, T, a, b, l, t, lane, first);
@@ -895,26 +846,12 @@ __device__ __forceinline__ const real2_t *tile_row(const real_t *base, long prow
 // its tile, keeping its pencil's rows of u0 in registers: u0 is read once instead of three times (9 field
 // passes instead of 11).  Needs der1st == der1st_sym and der2nd == der2nd_sym as lane tables (periodic
 // operators), so that all components use the same two table sets (tD1 for du and d(u conv), tD2 for d2u).
-#ifdef YT_TIMING
-// phase timing of k_ytile_transeq3 (scratch builds only): shader-clock ticks summed by wave 0 of every workgroup
-__device__ unsigned long long g_yt[8 + 32];  // [8..23]: per wave, ticks from component start to the end of its solves;
-                                             // [24..39]: per wave, ticks spent in the solves themselves
-extern "C" int x3d_debug_yt(unsigned long long *out, int reset)
-{
-    X3D_RANGE(__func__);
-    if (reset) { unsigned long long z[40] = {0}; return hipMemcpyToSymbol(HIP_SYMBOL(g_yt), z, sizeof z) != hipSuccess; }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_yt), sizeof(unsigned long long) * 40) != hipSuccess;
-}
-#define YT_T(k) do { if (threadIdx.x == 0) { const unsigned long long t_ = __builtin_readcyclecounter(); atomicAdd(&g_yt[k], t_ - yt_last); yt_last = t_; } } while (0)
-#else
-#define YT_T(k)
-#endif
 
 // UNI: both operators live on a uniform grid (stretch == 1, stretch_correct == 0 on every row): the ST / STC lane-table
 // reads and their multiplications are skipped (x * 1.0 and + nu * (x * 0.0): the same values).  The solves of this
 // kernel are bound by the RATE of LDS read instructions -- 2.6 clocks per ds_read_b64 and CU whatever the lanes read
 // (scratch/ldsbench.hip, round 4: broadcast, compressed and exec-masked reads cost the same), 236 table reads per lane
-// and component; without any table read the kernel runs at its memory time (2.30 -> 1.88 ms, -DXSCAN_EXP=4).
+// and component; without any table read the kernel runs at its memory time (2.30 -> 1.88 ms with the reads stubbed out).
 // P12 (with UNI): the component's first two solves -- d(u conv) and du, the SAME operator on two right-hand sides -- run
 // as ONE solve over the pair type V2: every table value read from LDS serves both (204 -> 136 reads per lane and
 // component) and the two dependency chains interleave.  Same arithmetic per right-hand side, bit for bit.
@@ -928,7 +865,7 @@ extern "C" int x3d_debug_yt(unsigned long long *out, int reset)
 // NPW (round 6): pencils per wave.  2 = a tile of 32 x-adjacent pencils, wave w solves pencils w and w + 16 one after the
 // other.  FP32: a row of the tile is then a 128-byte segment again (16 pencils of 4-byte reals are 64 bytes) and the
 // workgroup holds as many bytes in flight as a 512-row FP64 tile, at the same register counts (NI and the advecting rows
-// double, every value is half as wide).  256-row FP64 pencils: opt-in (ytile_npw)
+// double, every value is half as wide).  FP32 only (ytile_npw)
 // CIRC (round 6, with UNI, P12, local form): the circulant form of both operators (xscan_core.h, circ_solve; cD1 / cD2) -- no
 // lane tables are staged (the workgroup's LDS is its tile), no closure; results equal the table form's to round-off
 template <int Q, bool ACC, bool NARROW, bool HALO, bool UNI = false, bool P12 = false, bool EPI = false, int NPW = 1,
@@ -955,9 +892,6 @@ __global__ void __launch_bounds__(1024)
     // HALO: [16 pencils][8] halo values of the current field, then the same for the advecting velocity u0
     real_t *hal = tile + NPT * TP, *hal0 = hal + 128, *bnd = hal0 + 128;  // bnd: [16 pencils][9 ops][du_1, X_n]
     ntiles += tile0;  // tiles [tile0, tile0 + ntiles) (a range of planes: overlap of the neighbour exchange)
-#ifdef YT_TIMING
-    unsigned long long yt_last = __builtin_readcyclecounter();
-#endif
     int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int first = lane * Q + 1;
@@ -1005,18 +939,12 @@ __global__ void __launch_bounds__(1024)
 #pragma unroll 1
         for (int c = 0; c < 3; c++) {
             asm volatile("" : "+v"(lane));
-            YT_T(5);
-#ifdef YT_TIMING
-            const unsigned long long yt_c0 = __builtin_readcyclecounter();
-#endif
             to_tile(nxt);
             if (HALO && threadIdx.x < 128) {
                 hal[threadIdx.x] = hnx;
                 if (c == 0) hal0[threadIdx.x] = hnx;
             }
-            YT_T(0);
             __syncthreads();
-            YT_T(1);
             real2_t old[NI];
             [[maybe_unused]] real2_t bs[NI];
             [[maybe_unused]] TileEpi epi;
@@ -1090,10 +1018,6 @@ __global__ void __launch_bounds__(1024)
                 }
             };
             real_t r[Q], T[Q];
-            YT_T(2);
-#ifdef YT_TIMING
-            const unsigned long long yt_s0 = __builtin_readcyclecounter();
-#endif
             if constexpr (CIRC && !HALO) {
                 V2 w2[Q + 8], T2[Q];
 #pragma unroll
@@ -1160,15 +1084,6 @@ __global__ void __launch_bounds__(1024)
                     gload(old, o);
                     gload(bs, epi.base + off);
                 } else {
-                    YT_T(3);
-#ifdef YT_TIMING
-                    if (lane == 0) {
-                        const unsigned long long t_ = __builtin_readcyclecounter();
-                        atomicAdd(&g_yt[8 + wave], t_ - yt_c0);
-                        atomicAdd(&g_yt[24 + wave], t_ - yt_s0);
-                    }
-#endif
-#ifdef YT_NT
                     if (ACC) {
 #pragma unroll
                         for (int i = 0; i < NI; i++) {
@@ -1176,9 +1091,6 @@ __global__ void __launch_bounds__(1024)
                             old[i] = make_real2(__builtin_nontemporal_load(q_), __builtin_nontemporal_load(q_ + 1));
                         }
                     }
-#else
-                    if (ACC) gload(old, o);
-#endif
                 }
             }
             {
@@ -1217,24 +1129,18 @@ __global__ void __launch_bounds__(1024)
                     for (int i = 0; i < NI; i++) *const_cast<real2_t *>(tile_row<RP>(epi.y + off, prow, i, voff)) = bs[i];
                 } else {
                 __syncthreads();
-                YT_T(4);
 #pragma unroll
                 for (int i = 0; i < NI; i++) {
                     real2_t v = make_real2(tile[(2 * cc) * TP + cy + RP * i], tile[(2 * cc + 1) * TP + cy + RP * i]);
                     if (ACC) { v.x += old[i].x; v.y += old[i].y; }
-#ifdef YT_NT
                     {
                         real_t *q_ = reinterpret_cast<real_t *>(const_cast<real2_t *>(tile_row<RP>(o, prow, i, voff)));
                         __builtin_nontemporal_store(v.x, q_);
                         __builtin_nontemporal_store(v.y, q_ + 1);
                     }
-#else
-                    *const_cast<real2_t *>(tile_row<RP>(o, prow, i, voff)) = v;
-#endif
                 }
                 }  // (!EPI)
             }
-            YT_T(6);
             __syncthreads();  // the tile is free again
         }
         if (HALO && threadIdx.x < 288) {  // 16 pencils x 9 operators x {du_1, X_n} (the barrier above ordered them)
@@ -1260,7 +1166,8 @@ __global__ void __launch_bounds__(1024)
 // CIRC (round 6, with UNI, local form): both operators in the circulant form (circ_solve; ca / cb), no lane tables staged
 // CDUAL (with CIRC, MODE 0 / 1): the pair's two solves as ONE solve over the pair type with each operator's constants
 // (circ_pair): one pass through the phases, two dependency chains in flight.  Measured even (z-transforming mode 1 0.745 ->
-// 0.716 ms, mode 0 0.782 -> 0.794, plain pairs unchanged): only with X3D_CIRC_DUAL=1
+// 0.716 ms, mode 0 0.782 -> 0.794, plain pairs unchanged): taken for the z-transforming mode 1 only.  (The table form's
+// dual solve over both table sets measured no better: ZF mode 0 0.874 -> 0.905 ms, mode 1 0.773 -> 0.767.)
 template <int Q, int MODE, bool NARROW, bool HALO, bool ZF = false, bool UNI = false, bool CIRC = false, bool CDUAL = false>
 __global__ void __launch_bounds__(1024)
     k_ytile_tds_pair(real_t *out1, real_t *out2, const real_t *__restrict__ in1, const real_t *__restrict__ in2,
@@ -1333,13 +1240,6 @@ __global__ void __launch_bounds__(1024)
     // one operator on the window w: r = its tds_solve rows (der_univ_subs with the periodic self-exchange; HALO:
     // with recv_s = recv_e = 0, the own boundary values stored for the exchange -- see TileHalo)
     auto solve = [&](const real_t (&w)[Q + 8], real_t (&r)[Q], const real_t *__restrict__ l, const XOp &t, int op) {
-#if ZF_EXP & 2  // (timing experiment: no solve)
-        if constexpr (ZF) {
-#pragma unroll
-            for (int q = 0; q < Q; q++) r[q] = w[q + 4];
-            return;
-        }
-#endif
         if constexpr (CIRC && HALO) {
             real_t ab[2];
             if (op == 0) circ_solve<Q, NARROW, real_t, CircOp, true>(w, r, ca, lane, ab);
@@ -1444,16 +1344,6 @@ __global__ void __launch_bounds__(1024)
                 if (HALO && threadIdx.x < 128) hnx = hload(tn, 0);
             }
         }
-#ifdef XS_DUAL
-        // DUAL (round 5 experiment, OFF: measured no better -- ZF mode 0 0.874 -> 0.905 ms, mode 1 0.773 -> 0.767, step
-        // 43.07 -> 43.2 ms; profiles/r05_zf_pair_phases.txt): the pair's two solves -- different operators -- as ONE
-        // interleaved solve over both table sets (scan_solve_dual).  The solves are bound by the rate of LDS read
-        // instructions, which interleaving does not lower, and mode 0 loses the overlap of its first solve with the
-        // second input's trip through the tile.  Parity-green (30 pair / z-first / full-step tests).
-        constexpr bool DUAL = UNI && !HALO && MODE != 2;
-#else
-        constexpr bool DUAL = false;
-#endif
         if constexpr (CIRC && CDUAL && MODE != 2) {
             V2 w2[Q + 8], X2[Q];
             if (MODE == 0) {
@@ -1480,48 +1370,6 @@ __global__ void __launch_bounds__(1024)
             } else {
 #pragma unroll
                 for (int q = 0; q < Q; q++) { ra[q] = X2[q].a; rb[q] = X2[q].b; }
-                put(ra);
-                __syncthreads();
-                from_tile(out1 + off);
-                __syncthreads();  // out1's tile has been read
-                put(rb);
-                __syncthreads();
-                from_tile(out2 + off);
-            }
-        } else if constexpr (DUAL) {
-            V2 w2[Q + 8];
-            if (MODE == 0) {
-#pragma unroll
-                for (int m = 0; m < Q + 8; m++) w2[m].a = w[m];
-                to_tile(g2);
-                __syncthreads();
-                pick(b);
-                window_from_body<Q>(w, b, lane);
-#pragma unroll
-                for (int m = 0; m < Q + 8; m++) w2[m].b = w[m];
-            } else {
-#pragma unroll
-                for (int m = 0; m < Q + 8; m++) w2[m] = V2{w[m], w[m]};
-            }
-            V2 X2[Q], d1, xn2;
-            scan_solve_dual<Q, NARROW>(w2, X2, d1, xn2, la, lb, ta, tb, lane);
-            const real_t sa_ = ta.rs_s * (d1.a - ta.sa1 * xn2.a), ea_ = ta.rs_e * (xn2.a - ta.scn * d1.a);
-            const real_t sb_ = tb.rs_s * (d1.b - tb.sa1 * xn2.b), eb_ = tb.rs_e * (xn2.b - tb.scn * d1.b);
-#pragma unroll
-            for (int q = 0; q < Q; q++) {
-                ra[q] = X2[q].a - LTR(la, LT_SA(q)) * sa_ - LTR(la, LT_SC(q)) * ea_;
-                rb[q] = X2[q].b - LTR(lb, LT_SA(q)) * sb_ - LTR(lb, LT_SC(q)) * eb_;
-                if (q == 0) { ra[q] = (lane == 0) ? sa_ : ra[q]; rb[q] = (lane == 0) ? sb_ : rb[q]; }
-                if (q == Q - 1) { ra[q] = (lane == 63) ? ea_ : ra[q]; rb[q] = (lane == 63) ? eb_ : rb[q]; }
-            }
-            if (MODE == 0) {
-#pragma unroll
-                for (int q = 0; q < Q; q++) ra[q] = ra[q] + 1.0 * rb[q];
-                put(ra);
-                __syncthreads();
-                if constexpr (ZF) zf_forward<TP>(tile, tws, zf_row(tl), kzs, wave, lane);
-                else from_tile(out1 + tile_off_p(tl));
-            } else {
                 put(ra);
                 __syncthreads();
                 from_tile(out1 + off);
@@ -1562,7 +1410,7 @@ __global__ void __launch_bounds__(1024)
             __syncthreads();
             from_tile(out1 + off);
         }
-        }  // (!DUAL)
+        }  // (!CDUAL)
         if (HALO && threadIdx.x < 64) {  // 16 pencils x 2 operators x {du_1, X_n} (ordered by the barriers above)
             const int hw = threadIdx.x >> 2, k = threadIdx.x & 3;
             const long pp = (long)(tl / ntx) * (ntx * 16) + (long)(tl % ntx) * 16 + hw;
@@ -1660,14 +1508,6 @@ static bool circ_env_on()
     if (on < 0) { const char *e = getenv("X3D_NO_CIRC"); on = (e && e[0] == '1') ? 0 : 1; }
     return on == 1;
 }
-// the pair kernels' two circulant solves as one over the pair type (k_ytile_tds_pair<.., CDUAL>): X3D_CIRC_DUAL=1 everywhere,
-// default: the z-transforming mode 1 only
-static bool circ_dual_on()
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_CIRC_DUAL"); on = e ? (e[0] == '1') : 0; }
-    return on == 1;
-}
 // the HALO (decomposed-direction) forms in the circulant form: the same predicate picks the main kernel's solve AND the strip
 // kernel's tables, on every rank (the operators are the same everywhere).  X3D_NO_HALO_CIRC=1: the table form (A/B)
 static bool halo_circ(const x3d_tdsops *t)
@@ -1689,12 +1529,6 @@ static bool pair_halo_circ(const x3d_backend *b, int dir, const x3d_tdsops *ta, 
 static bool transeq_halo_circ(const x3d_backend *b, int dir, const x3d_tdsops *der1st, const x3d_tdsops *der2nd)
 {
     return b->ring[dir] && use_uniform_forms() && halo_circ(der1st) && halo_circ(der2nd);
-}
-static bool circ_dual_off()  // X3D_CIRC_DUAL=0: nowhere (A/B)
-{
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("X3D_CIRC_DUAL"); off = (e && e[0] == '0') ? 1 : 0; }
-    return off == 1;
 }
 
 static bool xscan_ok(const x3d_tdsops *t) { return t->tab.TL != nullptr && (t->tab.Q == 4 || t->tab.Q == 8); }
@@ -1741,7 +1575,7 @@ static int launch_transeq(x3d_backend *b, real_t *rhs, const real_t *u, const re
                           size_t lds, long pitch)
 {
     X3D_LDS_OPTIN(b, (k_xscan_transeq<Q, SAME, ACC, FAST>));  // > 64 KB of dynamic LDS needs the opt-in
-    hipLaunchKernelGGL((k_xscan_transeq<Q, SAME, ACC, FAST>), dim3(blocks), dim3(FAST ? XS_TQ_THREADS : 512), lds, b->stream, rhs, u, conv, xop_of(t1),
+    hipLaunchKernelGGL((k_xscan_transeq<Q, SAME, ACC, FAST>), dim3(blocks), dim3(FAST ? 1024 : 512), lds, b->stream, rhs, u, conv, xop_of(t1),
                        xop_of(t2), xop_of(t3), np, pitch, nu);
     X3D_HIP(hipGetLastError());
     return 0;
@@ -1966,28 +1800,22 @@ int x3d_ytile_tds_pair(x3d_backend *b, int dir, int mode, real_t *out1, real_t *
     if (ntiles <= 0) { *done = true; return 0; }
     const long rstride = dir == X3D_DIR_Y ? (long)b->nxp : pxy, ostride = dir == X3D_DIR_Y ? pxy : (long)b->nxp;
     if (128 * rstride * X3D_RB >= (1L << 32)) return 0;  // tile_row's 32-bit lane offset
-    static int cap = -1;
-    if (cap < 0) { const char *e = getenv("X3D_TILE_BLOCKS"); cap = e ? atoi(e) : 256; }
-    const int blocks = x3d_persistent_blocks(b, ntiles > cap ? cap : ntiles);
+    const int blocks = x3d_persistent_blocks(b, ntiles);
     const TileHalo th = halo ? *halo : TileHalo{nullptr, nullptr, 0, 0, 0, 0, 0};
     ProfScope ps(b, X3D_K_TDS_FWD, dir);
-#define GOD(Q_, M_, N_, H_, U_, C_, D_)                                                                         \
+#define GO(Q_, M_, N_, H_, U_, C_)                                                                              \
     do {                                                                                                        \
-        X3D_LDS_OPTIN(b, (k_ytile_tds_pair<Q_, M_, N_, H_, false, U_, C_, D_>));                                \
-        hipLaunchKernelGGL((k_ytile_tds_pair<Q_, M_, N_, H_, false, U_, C_, D_>), dim3(blocks), dim3(1024), lds, b->stream, out1, out2, \
+        X3D_LDS_OPTIN(b, (k_ytile_tds_pair<Q_, M_, N_, H_, false, U_, C_, false>));                             \
+        hipLaunchKernelGGL((k_ytile_tds_pair<Q_, M_, N_, H_, false, U_, C_, false>), dim3(blocks), dim3(1024), lds, b->stream, out1, out2, \
                            in1, in2, xop_of(ta), xop_of(tb), ntx, tile0, ntiles, rstride, ostride, th, permn,   \
                            ZfArg{}, ta->circ, tb->circ);                                                        \
     } while (0)
-#define GOC(Q_, M_, N_, H_, U_, C_) do { if ((C_) && (M_) != 2 && circ_dual_on()) GOD(Q_, M_, N_, H_, U_, C_, C_); else GOD(Q_, M_, N_, H_, U_, C_, false); } while (0)
-#define GO(Q_, M_, N_, H_, U_) GOC(Q_, M_, N_, H_, U_, false)
-#define GOH(Q_, M_, N_, U_) do { if (halo) GO(Q_, M_, N_, true, U_); else GO(Q_, M_, N_, false, U_); } while (0)
-#define GON(Q_, M_) do { if (circ && halo) GOD(Q_, M_, true, true, true, true, false); else if (circ) GOC(Q_, M_, true, false, true, true); else if (narrow && uni) GOH(Q_, M_, true, true); else if (narrow) GOH(Q_, M_, true, false); else GOH(Q_, M_, false, false); } while (0)
+#define GOH(Q_, M_, N_, U_) do { if (halo) GO(Q_, M_, N_, true, U_, false); else GO(Q_, M_, N_, false, U_, false); } while (0)
+#define GON(Q_, M_) do { if (circ && halo) GO(Q_, M_, true, true, true, true); else if (circ) GO(Q_, M_, true, false, true, true); else if (narrow && uni) GOH(Q_, M_, true, true); else if (narrow) GOH(Q_, M_, true, false); else GOH(Q_, M_, false, false); } while (0)
 #define GOM(Q_) do { if (mode == 0) GON(Q_, 0); else if (mode == 1) GON(Q_, 1); else GON(Q_, 2); } while (0)
     if (Q == 8) GOM(8); else GOM(4);
 #undef GOM
 #undef GON
-#undef GOC
-#undef GOD
 #undef GOH
 #undef GO
     if (halo) b->n_halo++;
@@ -2006,8 +1834,6 @@ bool x3d_zfirst_pairs_ok(const x3d_backend *b, const x3d_tdsops *ta, const x3d_t
     return 128 * (long)b->nxp * b->nyp * X3D_RB < (1L << 32);
 }
 
-int x3d_zfpair8(x3d_backend *b, int mode, real_t *out1, real_t *out2, const real_t *in1, const real_t *in2,
-                const x3d_tdsops *ta, const x3d_tdsops *tb, const ZfArg &zf, bool *done);  // zfpair8.hip
 // the z pairs next to the z-first Poisson solve (k_ytile_tds_pair<.., ZF>): mode 0: A(in1) + B(in2) -> spectrum,
 // mode 1: spectrum -> out1 = A(p), out2 = B(p); whole blocks of 512^3
 // y0, nyr: the tiles of the y rows [y0, y0 + nyr) only (nyr < 0: all) -- csrc/sfftz.hip cuts a solve into groups of y rows
@@ -2023,10 +1849,6 @@ int x3d_ytile_tds_pair_zf(x3d_backend *b, int mode, real_t *out1, real_t *out2, 
     X3D_REQUIRE(y0 >= 0 && nyr >= 0 && y0 + nyr <= zf.ny, "tds_pair (z-first): rows [%d, %d) of %d", y0, y0 + nyr, zf.ny);
     X3D_REQUIRE(zf.permn == 0 || (zf.permn == zf.ny && y0 == 0 && nyr == zf.ny), "tds_pair (z-first): interleaved rows, whole blocks only");
     if (nyr == 0) { *done = true; return 0; }
-    if (y0 == 0 && nyr == zf.ny) {  // whole blocks: the 8-pencil form, two workgroups per CU (zfpair8.hip)
-        if (int rc = x3d_zfpair8(b, mode, out1, out2, in1, in2, ta, tb, zf, done)) return rc;
-        if (*done) return 0;
-    }
     const bool narrow = stencil_narrow(ta) && stencil_narrow(tb);
     static int uni_on = -1;
     if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
@@ -2035,9 +1857,7 @@ int x3d_ytile_tds_pair_zf(x3d_backend *b, int mode, real_t *out1, real_t *out2, 
     const size_t lds = sizeof(real_t) * ((size_t)(circ ? 0 : 2 * LT_NC(8) * 64) + ZF_AREA_DOUBLES + 512);
     const long pxy = (long)b->nxp * b->nyp;
     const int ntx = b->nx / 16, ntiles = ntx * nyr, tile0 = ntx * y0;
-    static int cap = -1;
-    if (cap < 0) { const char *e = getenv("X3D_TILE_BLOCKS"); cap = e ? atoi(e) : 256; }
-    const int blocks = x3d_persistent_blocks(b, ntiles > cap ? cap : ntiles);
+    const int blocks = x3d_persistent_blocks(b, ntiles);
     const TileHalo th{nullptr, nullptr, 0, 0, 0, 0, 0};
     ProfScope ps(b, X3D_K_TDS_FWD, X3D_DIR_Z);
 #define GOD(M_, N_, U_, C_, D_)                                                                                 \
@@ -2047,7 +1867,7 @@ int x3d_ytile_tds_pair_zf(x3d_backend *b, int mode, real_t *out1, real_t *out2, 
                            out2, in1, in2, xop_of(ta), xop_of(tb), ntx, tile0, ntiles, pxy, (long)b->nxp, th, 0, zf, ta->circ, tb->circ); \
     } while (0)
 // (the dual solve where it measured faster: the z-transforming mode 1, 0.745 -> 0.716 ms; mode 0 0.782 -> 0.794: not)
-#define GO(M_, N_, U_, C_) do { if ((C_) && ((M_) == 1 || circ_dual_on()) && !circ_dual_off()) GOD(M_, N_, U_, C_, C_); else GOD(M_, N_, U_, C_, false); } while (0)
+#define GO(M_, N_, U_, C_) GOD(M_, N_, U_, C_, (C_) && (M_) == 1)
 #define GOU(M_) do { if (circ) GO(M_, true, true, true); else if (narrow && uni) GO(M_, true, true, false); else if (narrow) GO(M_, true, false, false); else GO(M_, false, false, false); } while (0)
     if (mode == 0) GOU(0); else GOU(1);
 #undef GOU
@@ -2102,17 +1922,15 @@ int x3d_transeq_halo_fix_launch(x3d_backend *b, int dir, real_t *const r[3], con
 }
 
 // pencils per wave of the tile kernels: 2 where a 16-pencil tile would move 64-byte row segments (FP32), local form, nx a
-// multiple of 32 (X3D_NO_NPW2=1: always 1).  256-row FP64 pencils (BASELINE configs[1]) with X3D_NPW2_256=1 only: measured
-// SLOWER there (5.24 against 5.04 ms per step at 256^3, k_ytile_transeq3<4> at 0.46 against 0.54 of the peak) -- a 256-row
-// solve costs what a 512-row one does less the per-row work (the scans, the reduced system), so two of them per wave double
-// the solve phase for the bytes of one 512-row tile: the 256-row tile is short of on-chip time, not of bytes in flight
-static int ytile_npw(const x3d_backend *b, int Q, bool halo)
+// multiple of 32 (X3D_NO_NPW2=1: always 1).  Not for 256-row FP64 pencils: measured slower (5.24 against 5.04 ms per step
+// at 256^3) -- two 256-row solves per wave double the solve phase for the bytes of one 512-row tile
+static int ytile_npw(const x3d_backend *b, bool halo)
 {
-    static int on = -1, on256 = -1;
+    static int on = -1;
     if (on < 0) { const char *e = getenv("X3D_NO_NPW2"); on = (e && e[0] == '1') ? 0 : 1; }
-    if (on256 < 0) { const char *e = getenv("X3D_NPW2_256"); on256 = (e && e[0] == '1') ? 1 : 0; }
-    return (on && !halo && b->nx % 32 == 0 && (X3D_RB == 4 || (Q == 4 && on256))) ? 2 : 1;
+    return (on && !halo && b->nx % 32 == 0 && X3D_RB == 4) ? 2 : 1;
 }
+constexpr int NPW2 = X3D_RB == 4 ? 2 : 1;  // the NPW of the launches where npw == 2 (no two-pencil forms are built for FP64)
 
 static bool ytile_circ(const x3d_tdsops *a, const x3d_tdsops *a2, const x3d_tdsops *c, const x3d_tdsops *c2)
 {
@@ -2135,7 +1953,7 @@ int x3d_ytile_transeq3(x3d_backend *b, int dir, real_t *const r[3], const real_t
     static int uni_on = -1;
     if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
     const bool uni = uni_on && der1st->uniform && der1st_sym->uniform && der2nd->uniform && der2nd_sym->uniform;
-    const int npw = (narrow && uni) ? ytile_npw(b, Q, halo != nullptr) : 1;  // (two pencils per wave: the uniform-grid forms)
+    const int npw = (narrow && uni) ? ytile_npw(b, halo != nullptr) : 1;  // (two pencils per wave: the uniform-grid forms)
     const bool circ = narrow && uni && (halo ? transeq_halo_circ(b, dir, der1st, der2nd) : ytile_circ(der1st, der1st_sym, der2nd, der2nd_sym));
     const size_t lds = sizeof(real_t) * ((size_t)(circ ? 0 : 2 * LT_N(Q) * 64) + 16 * npw * (64 * Q + 4) + (halo ? 256 + 288 : 0));
     if (lds > 160 * 1024) return 0;
@@ -2158,7 +1976,7 @@ int x3d_ytile_transeq3(x3d_backend *b, int dir, real_t *const r[3], const real_t
                            (const TileEpi *)nullptr, der1st->circ, der2nd->circ);                               \
     } while (0)
 #define GOC(Q_, A_, W_) do { if (circ) GOW(Q_, A_, true, false, true, W_, true); else GOW(Q_, A_, true, false, true, W_, false); } while (0)
-#define GO(Q_, A_, N_, H_, U_) do { if ((N_) && (U_) && !(H_)) { if (npw == 2) GOC(Q_, A_, 2); else GOC(Q_, A_, 1); } else if ((N_) && (U_) && (H_) && circ) GOW(Q_, A_, true, true, true, 1, true); else GOW(Q_, A_, N_, H_, U_, 1, false); } while (0)
+#define GO(Q_, A_, N_, H_, U_) do { if ((N_) && (U_) && !(H_)) { if (npw == 2) GOC(Q_, A_, NPW2); else GOC(Q_, A_, 1); } else if ((N_) && (U_) && (H_) && circ) GOW(Q_, A_, true, true, true, 1, true); else GOW(Q_, A_, N_, H_, U_, 1, false); } while (0)
 #define GOH(Q_, A_, N_, U_) do { if (halo) GO(Q_, A_, N_, true, U_); else GO(Q_, A_, N_, false, U_); } while (0)
 #define GON(Q_, A_) do { if (narrow && uni) GOH(Q_, A_, true, true); else if (narrow) GOH(Q_, A_, true, false); else GOH(Q_, A_, false, false); } while (0)
 #define GOA(Q_) do { if (acc) GON(Q_, true); else GON(Q_, false); } while (0)
@@ -2195,7 +2013,7 @@ int x3d_ytile_transeq3_epi(x3d_backend *b, int dir, real_t *const r[3], const re
     if (!on || !x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd)) return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
     const int Q = der1st->tab.Q;
-    const int npw = ytile_npw(b, Q, false);
+    const int npw = ytile_npw(b, false);
     // (FP64, 512 rows: the circulant form of THIS instantiation spills 14 VGPRs and runs at the table form's 3.1 ms; it is
     //  taken all the same -- the launch must give the bits of the plain z launch followed by the stage)
     const bool circ = ytile_circ(der1st, der1st_sym, der2nd, der2nd_sym);
@@ -2222,8 +2040,8 @@ int x3d_ytile_transeq3_epi(x3d_backend *b, int dir, real_t *const r[3], const re
                            ostride, nu, th, (const TileEpi *)b->epi_dev, der1st->circ, der2nd->circ);           \
     } while (0)
 #define GOEC(Q_, W_) do { if (circ) GOE(Q_, W_, true); else GOE(Q_, W_, false); } while (0)
-        if (Q == 8) { if (npw == 2) GOEC(8, 2); else GOEC(8, 1); }
-        else { if (npw == 2) GOEC(4, 2); else GOEC(4, 1); }
+        if (Q == 8) { if (npw == 2) GOEC(8, NPW2); else GOEC(8, 1); }
+        else { if (npw == 2) GOEC(4, NPW2); else GOEC(4, 1); }
 #undef GOEC
 #undef GOE
     }

@@ -3,15 +3,8 @@
 #pragma once
 #include "common.h"
 
-#ifndef XSCAN_EXP
-#define XSCAN_EXP 0  // timing experiments only (1: no stores, 2: no loads, 3: no scans)
-#endif
 // general form: TWO rows' stencil weights / table entries in flight instead of one (row q + 2's LDS reads wait for
 // row q's result, row q + 1's do not): +11 VGPRs, K3g's transeq_y 1.42 -> 1.37 ms per component at 257 rows.
-// -DXSCAN_CS_DEPTH1: one row at a time (A/B)
-#if !defined(XSCAN_CS_DEPTH1) && !defined(XSCAN_CS_DEPTH2)
-#define XSCAN_CS_DEPTH2
-#endif
 
 // lane-table entry indices (per operator): 8*Q row entries then the scan multipliers
 #define LT_F(q) (0 * Q + (q))
@@ -33,18 +26,12 @@
 // 4.3 against 2.6 LDS clocks per 512-byte row; MI355X_MICROARCH.md, LDS table) -- and these kernels are
 // LDS-bound on exactly these reads (LdsUtil 83 % in k_ytile_transeq3).  The empty asm is a barrier for the
 // load / store combiner only (it ends a merge window); it emits nothing.
-#if XSCAN_EXP == 4  // timing experiment: no lane-table reads at all (results are garbage): what the LDS reads cost
-__device__ __forceinline__ real_t lt_read(const real_t *__restrict__ l, int idx) { return 0.37 + 1e-3 * (idx & 7); }
-#elif !defined(XS_READ2)
 __device__ __forceinline__ real_t lt_read(const real_t *__restrict__ l, int idx)
 {
     const real_t v = l[idx];
     asm volatile("" ::: "memory");
     return v;
 }
-#else
-__device__ __forceinline__ real_t lt_read(const real_t *__restrict__ l, int idx) { return l[idx]; }
-#endif
 #define LTR(l, e) lt_read((l), (e) * 64 + lane)
 
 // Compressed lane tables (LS = LTC_LS instead of 64; xwide.hip, 1024-row pencils: Q = 16 would need 80 KB per
@@ -124,10 +111,8 @@ __device__ __forceinline__ real_t readlane_d(real_t v, int l)
 // FP32 (round 6): the pair IS a packed register pair -- gfx950 runs v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 at the rate
 // of their scalar forms, so a pair solve costs the vector instructions of ONE solve (the FP32 flavour moves half the bytes
 // with the FP64 flavour's instruction count otherwise: it is bound by instruction issue, not by HBM).  Same operations per
-// component, same rounding (a packed FMA is two FMAs).  X3D_SP_NO_PK: the two-scalars form (A/B)
-#ifndef X3D_SP_NO_PK
+// component, same rounding (a packed FMA is two FMAs).
 #define X3D_V2_PACKED 1
-#endif
 #endif
 #ifdef X3D_V2_PACKED
 typedef float x3d_f2 __attribute__((ext_vector_type(2)));
@@ -234,12 +219,8 @@ __device__ __forceinline__ void scan_solve(const T (&w)[Q + 8], T (&X)[Q], T &du
     if constexpr (!FAST) {
         const int ls = (nr - 4) / Q;
         int co = (lane == 0 ? 0 : (lane == ls ? 1 : (lane == ls + 1 ? 2 : 3))) * (Q * 10);
-#ifdef XSCAN_CS_DEPTH2
         // (the pair type with the wide stencils: one row at a time -- two rows' ten weights each do not fit beside two windows)
         constexpr bool D2 = NARROW || sizeof(T) == sizeof(real_t);
-#else
-        constexpr bool D2 = false;
-#endif
         int co1 = co;  // two rows' weights in flight: row q + 2's reads wait for acc[q], row q + 1's do not
         if constexpr (D2) asm volatile("" : "+v"(co1));
 #pragma unroll
@@ -267,9 +248,6 @@ __device__ __forceinline__ void scan_solve(const T (&w)[Q + 8], T (&X)[Q], T &du
     // ---- scan of the lane-end values, then carry-in = true e at the end of lane l-1
     T v = prev;
     PHASE(X[Q / 2]);
-#if XSCAN_EXP == 3
-    T carry = v;
-#else
     // prefix scan without LDS traffic: in-row Kogge-Stone by DPP row shifts, then lane 15 / 47 into rows
     // 1 / 3 and lane 31 into rows 2, 3 (row_bcast); lanes without a source read 0.  (The row_bcast moves run with
     // all rows enabled: the rows that are not meant to receive carry a multiplier of exactly 0 in the tables,
@@ -281,7 +259,6 @@ __device__ __forceinline__ void scan_solve(const T (&w)[Q + 8], T (&X)[Q], T &du
     v += LTM(lt, 4) * dpp0<0x142>(v);
     v += LTM(lt, 5) * dpp0<0x143>(v);
     T carry = dpp0<0x138>(v);  // wave_shr:1
-#endif
     // ---- apply, lane-local back-substitution from zero
     T nxt = zero_of<T>();
     PHASE(carry);
@@ -293,9 +270,6 @@ __device__ __forceinline__ void scan_solve(const T (&w)[Q + 8], T (&X)[Q], T &du
     if (n == nr) {}  // (row n_rhs = n+1 of a v2p operator carries F = H = 0 in the tables)
     v = nxt;
     PHASE(X[Q / 2]);
-#if XSCAN_EXP == 3
-    carry = v;
-#else
     // suffix scan: row shifts the other way, then lane 16 / 48 into rows 0 / 2 and lane 32 into rows 0, 1
     v += LTM(lt, 6 + 0) * dpp0<0x101>(v);
     v += LTM(lt, 6 + 1) * dpp0<0x102>(v);
@@ -307,7 +281,6 @@ __device__ __forceinline__ void scan_solve(const T (&w)[Q + 8], T (&X)[Q], T &du
         v += LTM(lt, 6 + 5) * readlane_d(v, 32);
     }
     carry = dpp0<0x130>(v);  // wave_shl:1
-#endif
 #pragma unroll
     for (int q = 0; q < Q; q++) X[q] = X[q] + LTX(lt, LT_QB(q)) * carry;
     // du_1 = last_r * X_1 (X_1 = e_1 - bw_1 X_2, distributed.f90:161-166); X_n = e_n
@@ -338,12 +311,7 @@ __device__ __forceinline__ void scan_solve(const T (&w)[Q + 8], T (&X)[Q], T &du
 // enters through its first (last) lane by a wave rotate, which also closes the ring (lane 0 <- lane 63: the periodic wrap
 // needs no closure at all), and spreads along the row by the same shifts.  Per right-hand side at Q = 8, 5-tap stencil:
 // ~118 vector instructions and NO LDS reads (scan_solve's periodic form + substitution: ~150 and 68).
-#ifdef CIRC_SCHED  // (experiment: scheduling barriers between the phases -- the EPI form of k_ytile_transeq3 then fits its
-                   //  128 VGPRs (14 spilled without), and runs SLOWER: 3.33 against 3.11 ms; the y launch 1.86 against 1.72)
-#define CIRC_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define CIRC_SB()
-#endif
+// (Scheduling barriers between the phases measured slower: the EPI form of k_ytile_transeq3 3.33 against 3.11 ms.)
 // CircOp2: TWO operators side by side -- the pair type's two right-hand sides each take their own constants (the operator
 // pairs of the pressure correction: different operators on the same or on two inputs, ONE pass through the phases, two
 // independent dependency chains in flight)
@@ -387,7 +355,6 @@ __device__ __forceinline__ void circ_solve(const T (&w)[Q + 8], T (&X)[Q], const
         }
     }
     const bool row_first = (lane & 15) == 0, row_last = (lane & 15) == 15;
-    CIRC_SB();
     T prev = zero_of<T>();
 #pragma unroll
     for (int q = 0; q < Q; q++) {
@@ -395,7 +362,6 @@ __device__ __forceinline__ void circ_solve(const T (&w)[Q + 8], T (&X)[Q], const
         prev = X[q];
     }
     T v = prev;
-    CIRC_SB();
     v = fma_of(m1, dpp0<0x111>(v), v);  // row_shr:1, 2, 4 (, 8): lanes without a source read 0
     v = fma_of(m2, dpp0<0x112>(v), v);
     v = fma_of(m4, dpp0<0x114>(v), v);
@@ -417,7 +383,6 @@ __device__ __forceinline__ void circ_solve(const T (&w)[Q + 8], T (&X)[Q], const
         bnd[1] = E;
         endc = t.phi0 * E;
     }
-    CIRC_SB();
     // (16 rows per lane, the 1024-row x pencils: (-rho)^(q + 1) = (-rho)^(q - 7) (-rho)^8 for the upper eight rows)
     T carry8 = zero_of<T>();
     if constexpr (Q > 8) carry8 = t.pf[7] * carry;
@@ -427,7 +392,6 @@ __device__ __forceinline__ void circ_solve(const T (&w)[Q + 8], T (&X)[Q], const
         nxt = X[q];
     }
     v = nxt;
-    CIRC_SB();
     v = fma_of(m1, dpp0<0x101>(v), v);  // row_shl:1, 2, 4 (, 8)
     v = fma_of(m2, dpp0<0x102>(v), v);
     v = fma_of(m4, dpp0<0x104>(v), v);
@@ -442,7 +406,6 @@ __device__ __forceinline__ void circ_solve(const T (&w)[Q + 8], T (&X)[Q], const
         v = fma_of(m1, z, v);
     }
     carry = OPEN ? sel_of(lane == 63, endc, dpp0<0x130>(v)) : dpp0<0x134>(v);
-    CIRC_SB();
     if constexpr (Q > 8) carry8 = t.pf[7] * carry;
 #pragma unroll
     for (int q = 0; q < Q; q++) {
@@ -450,76 +413,6 @@ __device__ __forceinline__ void circ_solve(const T (&w)[Q + 8], T (&X)[Q], const
         X[q] = k < 8 ? fma_of(t.pf[k], carry, X[q]) : fma_of(t.pf[k - 8], carry8, X[q]);
     }
     if constexpr (OPEN) bnd[0] = readlane_d(X[0], 0);
-}
-
-// Two DIFFERENT operators (lane tables la / lb, descriptors ta / tb) on two right-hand sides (w[.].a, w[.].b) as ONE
-// interleaved solve -- the FAST (periodic-type) form of scan_solve with every table value read per operator: the same
-// number of LDS reads as two solves one after the other, but two independent dependency chains in flight and one pass
-// through the scan's phases (round 5: the z-transforming operator pairs are bound by their serial on-chip chain,
-// profiles/r05_zf_pair_phases.txt).  Arithmetic per right-hand side = scan_solve<Q, true, NARROW>, expression by expression.
-template <int Q, bool NARROW>
-__device__ __forceinline__ void scan_solve_dual(const V2 (&w)[Q + 8], V2 (&X)[Q], V2 &du1, V2 &xn,
-                                                const real_t *__restrict__ la, const real_t *__restrict__ lb, const XOp &ta,
-                                                const XOp &tb, int &lane)
-{
-#define PHASE2(x) asm volatile("" : "+v"(lane) : "v"((x).a))
-#define L2(e) V2{lt_read(la, (e) * 64 + lane), lt_read(lb, (e) * 64 + lane)}
-    V2 acc[Q];
-    if (NARROW) {
-        const V2 c2{ta.c[2], tb.c[2]}, c3{ta.c[3], tb.c[3]}, c4{ta.c[4], tb.c[4]}, c5{ta.c[5], tb.c[5]}, c6{ta.c[6], tb.c[6]};
-#pragma unroll
-        for (int q = 0; q < Q; q++)
-            acc[q] = c2 * w[q + 2] + c3 * w[q + 3] + c4 * w[q + 4] + c5 * w[q + 5] + c6 * w[q + 6];
-    } else {
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            V2 a = V2{ta.c[0], tb.c[0]} * w[q];
-#pragma unroll
-            for (int m = 1; m < 9; m++) a = a + V2{ta.c[m], tb.c[m]} * w[q + m];
-            acc[q] = a;
-        }
-    }
-    V2 prev = zero_of<V2>();
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        X[q] = L2(LT_F(q)) * (acc[q] - L2(LT_A(q)) * prev);
-        prev = X[q];
-    }
-    V2 v = prev;
-    PHASE2(X[Q / 2]);
-    v += L2(LT_MF(0)) * dpp0<0x111>(v);
-    v += L2(LT_MF(1)) * dpp0<0x112>(v);
-    v += L2(LT_MF(2)) * dpp0<0x114>(v);
-    v += L2(LT_MF(3)) * dpp0<0x118>(v);
-    v += L2(LT_MF(4)) * dpp0<0x142>(v);
-    v += L2(LT_MF(5)) * dpp0<0x143>(v);
-    V2 carry = dpp0<0x138>(v);  // wave_shr:1
-    V2 nxt = zero_of<V2>();
-    PHASE2(carry);
-#pragma unroll
-    for (int q = Q - 1; q >= 0; q--) {
-        X[q] = (X[q] + L2(LT_PF(q)) * carry) + L2(LT_H(q)) * nxt;
-        nxt = X[q];
-    }
-    v = nxt;
-    PHASE2(X[Q / 2]);
-    v += L2(LT_MB(0)) * dpp0<0x101>(v);
-    v += L2(LT_MB(1)) * dpp0<0x102>(v);
-    v += L2(LT_MB(2)) * dpp0<0x104>(v);
-    v += L2(LT_MB(3)) * dpp0<0x108>(v);
-    {
-        const V2 s16 = readlane_d(v, 16), s48 = readlane_d(v, 48);
-        v += L2(LT_MB(4)) * sel_of(lane < 32, s16, s48);
-        v += L2(LT_MB(5)) * readlane_d(v, 32);
-    }
-    carry = dpp0<0x130>(v);  // wave_shl:1
-#pragma unroll
-    for (int q = 0; q < Q; q++) X[q] = X[q] + L2(LT_QB(q)) * carry;
-    du1 = V2{ta.last_r, tb.last_r} * readlane_d(X[0], 0);
-    xn = readlane_d(X[Q - 1], 63);
-    PHASE2(xn);
-#undef PHASE2
-#undef L2
 }
 
 // nr == 64*Q and n_wrap == nr: every lane's body is a full aligned vector and the halos are
@@ -573,39 +466,11 @@ __device__ __forceinline__ void rotl_pairs(real_t &a0, real_t &a1, real_t &b0, r
     b0 = r2 ? d0 : b0; b1 = r2 ? d1 : b1;
     d0 = r2 ? t0 : d0; d1 = r2 ? t1 : d1;
 }
-// XS_TLOAD (experiment, round 4): the lane's 64 bytes fetched as whole 64-byte sectors per instruction (instruction m
-// takes piece 4 m + j of the quad's 256 bytes) and transposed back by the quad; 2: with the nontemporal hint
-#ifndef XS_TLOAD
-#define XS_TLOAD 0
-#endif
-__device__ __forceinline__ void load_body_q8t(real_t (&b)[8], const real_t *__restrict__ row, int lane)
-{
-    const int j = lane & 3;
-    const real_t *__restrict__ q = row + (lane & ~3) * 8 + 2 * j;
-#if XS_TLOAD == 2
-    const real2_t *__restrict__ qs = reinterpret_cast<const real2_t *>(q);
-    const real2_t v0 = ldg_stream(qs), v1 = ldg_stream(qs + 4), v2 = ldg_stream(qs + 8), v3 = ldg_stream(qs + 12);
-#else
-    const real2_t *__restrict__ q2 = reinterpret_cast<const real2_t *>(q);
-    const real2_t v0 = q2[0], v1 = q2[4], v2 = q2[8], v3 = q2[12];
-#endif
-    real_t a0 = v0.x, a1 = v0.y, b0 = v1.x, b1 = v1.y, c0 = v2.x, c1 = v2.y, d0 = v3.x, d1 = v3.y;
-    rotl_pairs(a0, a1, b0, b1, c0, c1, d0, d1, j);
-    b0 = dpp_quad(b0, 1); b1 = dpp_quad(b1, 1);
-    c0 = dpp_quad(c0, 2); c1 = dpp_quad(c1, 2);
-    d0 = dpp_quad(d0, 3); d1 = dpp_quad(d1, 3);
-    rotl_pairs(a0, a1, b0, b1, c0, c1, d0, d1, j);
-    b[0] = a0; b[1] = a1; b[2] = d0; b[3] = d1; b[4] = c0; b[5] = c1; b[6] = b0; b[7] = b1;
-}
-
 // FAST path: only the lane's own Q rows come from memory (4 aligned 16-byte loads, issued one
 // pencil ahead); the 4+4 halo rows are the neighbour lanes' rows (periodic wrap across the wave)
 template <int Q>
 __device__ __forceinline__ void load_body(real_t (&b)[Q], const real_t *__restrict__ row, int lane)
 {
-#if XS_TLOAD
-    if constexpr (Q == 8) { load_body_q8t(b, row, lane); return; }
-#endif
     const real2_t *__restrict__ body = reinterpret_cast<const real2_t *>(row + lane * Q);
 #pragma unroll
     for (int m = 0; m < Q / 2; m++) {

@@ -22,9 +22,9 @@
 //            two halves of 25 KB); wave 0 runs the 32 chains (x 0..7, re / im, odd / even system), k_penta_solve's
 //            arithmetic operation by operation.  DEFAULT                                                    11.4 ms
 //            (without the chains -- wrong results, timing only -- 9.9: they cost 0.5 ms per solve; 2 workgroups per CU)
-//   "fused"  k_y010<2>: everything in one kernel, 72 B per entry, the chains stream the operator from memory themselves:
-//            23.1 ms -- 32 lanes wait a full memory latency per 8-row chunk, 32 times per tile.  Kept as the measured
-//            negative; parity-green like the others.
+//   "fused"  (removed; its code last lived at commit ca23787) everything in one kernel, 72 B per entry, the chains stream
+//            the operator from memory themselves: 23.1 ms -- 32 lanes wait a full memory latency per 8-row chunk, 32 times
+//            per tile.
 #include <type_traits>
 
 #include "fft512_core.h"
@@ -99,103 +99,6 @@ __device__ __forceinline__ void y010_pair_bw(real2_t *__restrict__ pen, int j0, 
     if (paired && !self) pen[jr0] = make_real2(r_r, r_c);
 }
 
-// k_penta_solve (spectral010.h) on the tile in LDS: this lane's chain = component `ri` of column x, system s
-// (sym: rows 2 j + s - 2, 0-based, j = 1 .. n = 128; else all 256 rows)
-__device__ __forceinline__ void y010_penta(real2_t *__restrict__ sm, const Y010Arg &g, int kz, int x0, int lane)
-{
-    constexpr int ny = 256, U = 8;
-    const int x = lane & 7, ri = (lane >> 3) & 1, s = lane >> 4;
-    if (s >= (g.sym ? 2 : 1)) return;
-    const int inc = g.sym ? 2 : 1, n = ny / inc;
-    const real_t *__restrict__ lu = s ? g.lu1 : g.lu0;
-    const size_t ds = (size_t)g.nzl * n * g.nxs;
-    const real_t *__restrict__ lub = lu + (size_t)kz * n * g.nxs + x0 + x;
-#define LU(j, d) lub[(size_t)((d) - 1) * ds + (size_t)((j) - 1) * g.nxs]
-    real_t *__restrict__ pd = reinterpret_cast<real_t *>(sm + x * Y010_P) + ri;
-#define C(j) pd[2 * (inc * (j) + s - inc)]  // (inc j + off - h - 1 with off = s, h = inc / 2: 2 j + s - 2 or j - 1)
-    const real_t eps = 1.e-16;
-    // forward: rows j+1, j+2 -= m * row j; two rows are carried in registers
-    real_t r0 = C(1), r1 = C(2);
-    real_t m1c[U], m2c[U], m1n[U], m2n[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int j = 1 + u;
-        m1c[u] = j <= n - 2 ? LU(j, 2) : 0.0;
-        m2c[u] = j <= n - 2 ? LU(j, 1) : 0.0;
-    }
-    for (int jb = 1; jb <= n - 2; jb += U) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int j = jb + U + u;
-            m1n[u] = j <= n - 2 ? LU(j, 2) : 0.0;
-            m2n[u] = j <= n - 2 ? LU(j, 1) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int j = jb + u;
-            if (j <= n - 2) {
-                real_t r2 = C(j + 2);
-                r1 = r1 - m1c[u] * r0;
-                r2 = r2 - m2c[u] * r0;
-                C(j) = r0;
-                r0 = r1; r1 = r2;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) { m1c[u] = m1n[u]; m2c[u] = m2n[u]; }
-    }
-    // last two rows: r0 = row n-1, r1 = row n
-    const real_t tmp = LU(n - 1, 2), dd = LU(n, 3), inv = LU(n - 1, 3), a4n = LU(n - 1, 4);
-    // (the first backward chunk, requested before the divisions)
-    real_t ivc[U], a4c[U], a5c[U], ivn[U], a4x[U], a5n[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int j = n - 2 - u;
-        ivc[u] = j >= 1 ? LU(j, 3) : 0.0;
-        a4c[u] = j >= 1 ? LU(j, 4) : 0.0;
-        a5c[u] = j >= 1 ? LU(j, 5) : 0.0;
-    }
-    real_t xn, xn1;
-    if (fabs(dd) > eps) {
-        const real_t tt = tmp / dd;
-        xn = r1 / dd - tt * r0;
-    } else {
-        xn = 0.0;
-    }
-    const real_t q = a4n * inv;
-    xn1 = r0 * inv - xn * q;
-    const bool zero_line = (x0 + x + 1) == g.nx / 2 + 1 && (kz + 1) == g.nz / 2 + 1;
-    if (zero_line) { xn = 0.0; xn1 = 0.0; }
-    C(n) = xn;
-    C(n - 1) = xn1;
-    // backward
-    real_t x1 = xn1, x2 = xn;
-    for (int jb = n - 2; jb >= 1; jb -= U) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int j = jb - U - u;
-            ivn[u] = j >= 1 ? LU(j, 3) : 0.0;
-            a4x[u] = j >= 1 ? LU(j, 4) : 0.0;
-            a5n[u] = j >= 1 ? LU(j, 5) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int j = jb - u;
-            if (j >= 1) {
-                const real_t r = C(j);
-                real_t xv = ivc[u] * (r - a4c[u] * x1 - a5c[u] * x2);
-                if (zero_line) xv = 0.0;
-                C(j) = xv;
-                x2 = x1; x1 = xv;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) { ivc[u] = ivn[u]; a4c[u] = a4x[u]; a5c[u] = a5n[u]; }
-    }
-#undef LU
-#undef C
-}
-
 // ---- MODES 3 / 4: the sweeps of k_penta_solve on the tile with the operator STAGED in LDS by all 512 threads.
 // Row slots: R = s n + (j - 1) in 0 .. 255 (sym: two systems of n = 128 rows; else one of 256); a thread stages
 // (x = t & 7, R = (t >> 3) + 64 h, h = 0 .. 3) of every diagonal: one 64-byte segment per row.
@@ -216,11 +119,7 @@ __device__ __forceinline__ Y010Chain y010_chain(real2_t *__restrict__ sm, const 
     Y010Chain c;
     c.x = lane & 7;
     c.s = (lane >> 4) & 1;
-#ifdef Y010_NO_SWEEP  // (timing experiment: what the two kernels take without their chains)
-    c.on = false;
-#else
     c.on = wave == 0 && lane < 32 && c.s < (SYM ? 2 : 1);
-#endif
     c.pd = reinterpret_cast<real_t *>(sm + c.x * Y010_P) + ((lane >> 3) & 1) + 2 * c.s;
     c.zero_line = (x0 + c.x + 1) == g.nx / 2 + 1 && (kz + 1) == g.nz / 2 + 1;
     return c;
@@ -477,11 +376,6 @@ __global__ void __launch_bounds__(512) k_y010(real2_t *__restrict__ c, const rea
         if (lane == 0) y010_pair_fw(pen, 128, rz, rx, g.ay, g.by, g.nx, g.nz);
         wave_lds_fence();
     }
-    if (MODE == 2) {
-        __syncthreads();
-        if (wave == 0 && lane < 32) y010_penta(sm, g, kz, x0, lane);
-        __syncthreads();
-    }
     if constexpr (MODE == 3) {  // forward sweeps on the tile, both diagonals staged whole
 #pragma unroll
         for (int h = 0; h < 4; h++) {
@@ -554,7 +448,7 @@ __global__ void __launch_bounds__(512) k_y010(real2_t *__restrict__ c, const rea
 const real2_t *x3d_fft512_twiddles();
 int x3d_fft512_init();
 
-// c[nz][256][nxs], x and z already transformed (mode 0, 2) / still transformed (mode 1, 2).  tables = ax bx ay by az bz
+// c[nz][256][nxs], x and z already transformed (mode 0, 3) / still transformed (mode 1, 4).  tables = ax bx ay by az bz
 // back to back (global lengths nx nx ny ny nz nz).  *done = false: not served (other ny, odd row pitch)
 // nzl (0: nz): the z planes c and lu hold -- nz / 2 + 1 with every x mode for the z-first layout
 int x3d_y010_run(x3d_backend *b, real2_t *c, int nxs, int nx, int ny, int nz, int mode, const real_t *tables, int sym,
@@ -579,7 +473,7 @@ int x3d_y010_run(x3d_backend *b, real2_t *c, int nxs, int nx, int ny, int nz, in
         X3D_LDS_OPTIN(b, (k_y010<M_>));                                                                \
         hipLaunchKernelGGL((k_y010<M_>), grid, dim3(512), lds, b->stream, c, x3d_fft512_twiddles(), g); \
     } while (0)
-    if (mode == 0) GO(0); else if (mode == 1) GO(1); else if (mode == 2) GO(2); else if (mode == 3) GO(3); else GO(4);
+    if (mode == 0) GO(0); else if (mode == 1) GO(1); else if (mode == 3) GO(3); else GO(4);
 #undef GO
     X3D_HIP(hipGetLastError());
     *done = true;
