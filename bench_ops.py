@@ -6,7 +6,14 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats]
+
+Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
+--stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
+(x3d_stats_profile_sums + _accumulate, 24 B/DoF), the same nine running means composed from veccopy / vecmult / vecadd
+(456 B/DoF: what the entry points of the reference's backend interface cost), and the existing reduction
+x3d_scalar_product on the same field (16 B/DoF).  GB/s on those stated bytes; `ceiling` = fraction of the 6.2 TB/s copy
+ceiling (profiles/r04_copy_ceiling.txt).
 """
 import argparse
 import json
@@ -20,12 +27,83 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
+def bench_stats(args):
+    """one JSON line per (op, n) of the "statistics sample" family"""
+    import ctypes
+
+    import torch
+    from x3d2_amd import Mesh, _lib
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.common import DIR_X, VERT
+    per = ("periodic",) * 2
+    rb = 4 if _lib.SINGLE else 8
+    for n in (256, 512):
+        mesh = Mesh((n, n, n), (1, 1, 1), (6.283185307179586,) * 3, per, per, per)
+        b = HipBackend(mesh)
+        al = b.allocator
+        u, v, w, tmp = (al.get_block(DIR_X, VERT) for _ in range(4))
+        means = [al.get_block(DIR_X, VERT) for _ in range(9)]
+        rng = np.random.default_rng(0)
+        for f in (u, v, w):
+            b.set_field_data(f, rng.standard_normal((n, n, n), dtype=np.float32))
+        for f in means:
+            f.fill(0.0)
+        prof, sums = (torch.zeros(9 * n, dtype=_lib.torch_real(), device=b.device) for _ in range(2))
+        dof, inc = n ** 3, 0.125
+
+        def composed():
+            for x, m in zip((u, v, w), means[:3]):
+                b.vecadd(inc, x, 1.0 - inc, m)
+            for (x, y), m in zip(((u, u), (v, v), (w, w), (u, v), (u, w), (v, w)), means[3:]):
+                b.veccopy(tmp, x)
+                b.vecmult(tmp, y)
+                b.vecadd(inc, tmp, 1.0 - inc, m)
+
+        def profile():
+            b.stats_profile_sums(u, v, w, 2, sums)
+            b.stats_profile_accumulate(prof, sums, 1.0 / (n * n), inc)
+
+        cases = (("statistics sample: fused 3-D update", lambda: b.stats_update_uvw(u, v, w, means, inc), 21),
+                 ("statistics sample: composed from veccopy/vecmult/vecadd", composed, 57),
+                 ("statistics sample: profile update (dir_keep = y)", profile, 3),
+                 ("scalar_product (k_reduce) on the same field", lambda: b.scalar_product(u, v), 2))
+        ms_of = {}
+        for name, fn, reals in cases:
+            ms = ctypes.c_float()
+            times = []
+            for i in range(args.stat_warmup + args.stat_iters):
+                _lib.check(b.lib.x3d_timer_start(b.h))
+                fn()
+                _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+                if i >= args.stat_warmup:
+                    times.append(ms.value)
+            t = float(np.median(times))
+            ms_of[name] = t
+            gbs = reals * rb * dof / t / 1e6
+            row = {"op": name, "n": n, "real_bytes": rb, "ms_median": t, "ms_min": float(min(times)), "launches": len(times),
+                   "bytes_per_dof": reals * rb, "GBs": gbs, "ceiling": gbs / 6200.0}
+            if name.endswith("fused 3-D update"):
+                fused = t
+            if "composed" in name:
+                row["fused_over_composed"] = fused / t
+            print(json.dumps(row))
+        del b, al, u, v, w, tmp, means
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats"))
+    ap.add_argument("--stat-iters", type=int, default=30)
+    ap.add_argument("--stat-warmup", type=int, default=5)
     args = ap.parse_args()
+    if args.family in ("all", "stats"):
+        bench_stats(args)
+    if args.family == "stats":
+        return
     import torch
     from x3d2_amd import Mesh
     from x3d2_amd.backend import HipBackend

@@ -617,6 +617,42 @@ module m_x3d2_hip_capi
       import :: c_ptr, c_int
       type(c_ptr), value :: p, f
     end function
+    ! flow statistics on the device (include/x3d2_hip.h, "flow statistics"): stats_manager_t%update / write_stats
+    ! (src/io/stats.f90:118-187, 232-237) without the host copies; mean = 9 device blocks in the order
+    ! u, v, w, uu, vv, ww, uv, uw, vw
+    integer(c_int) function x3d_stats_update_uvw(b, u, v, w, mean, stat_inc) bind(C, name='x3d_stats_update_uvw')
+      import :: c_ptr, c_int, x3d_creal
+      type(c_ptr), value :: b, u, v, w
+      type(c_ptr), intent(in) :: mean(9)
+      real(x3d_creal), value :: stat_inc
+    end function
+    ! mean_phiphi = c_null_ptr: first moment only
+    integer(c_int) function x3d_stats_update_scalar(b, phi, mean_phi, mean_phiphi, stat_inc) &
+      bind(C, name='x3d_stats_update_scalar')
+      import :: c_ptr, c_int, x3d_creal
+      type(c_ptr), value :: b, phi, mean_phi, mean_phiphi
+      real(x3d_creal), value :: stat_inc
+    end function
+    integer(c_int) function x3d_stats_derive(b, out, mean) bind(C, name='x3d_stats_derive')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: b
+      type(c_ptr), intent(in) :: out(6), mean(9)
+    end function
+    ! sums: device buffer of 9 * dims(dir_keep) reals (x3d_device_alloc)
+    integer(c_int) function x3d_stats_profile_sums(b, u, v, w, dims, dir_keep, sums) &
+      bind(C, name='x3d_stats_profile_sums')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: b, u, v, w, sums
+      integer(c_int), intent(in) :: dims(3)
+      integer(c_int), value :: dir_keep
+    end function
+    integer(c_int) function x3d_stats_profile_accumulate(b, prof, sums, n, scale, stat_inc) &
+      bind(C, name='x3d_stats_profile_accumulate')
+      import :: c_ptr, c_int, c_long, x3d_creal
+      type(c_ptr), value :: b, prof, sums
+      integer(c_long), value :: n
+      real(x3d_creal), value :: scale, stat_inc
+    end function
   end interface
 
 contains

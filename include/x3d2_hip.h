@@ -703,6 +703,31 @@ typedef int (*x3d_dist_tds_fn)(void *user, int dir, int mode, x3d_real *out1, x3
                                const x3d_real *in2, const x3d_tdsops *ta, const x3d_tdsops *tb);
 int x3d_lazy_set_dist_tds(x3d_backend *b, unsigned dir_mask, x3d_dist_tds_fn fn, void *user);
 
+/* ---- flow statistics on the device (csrc/stats.hip): stats_manager_t, src/io/stats.f90.  The reference copies u, v, w to
+ * the host at every sample (:139-141) and updates nine host arrays there; here the accumulators are ordinary blocks
+ * (x3d_block_alloc, zero-filled by the caller) and a sample is one launch.  Moment order everywhere, as :151-159:
+ * u, v, w, uu, vv, ww, uv, uw, vw.  All fields at VERT (:15-16).  No call synchronises with the host. */
+/* stats_manager_t%update, :143-159: mean[k] += (val_k - mean[k]) * stat_inc (accumulate_mean, :61-70) for the nine moments,
+ * whole padded blocks.  The nine accumulators must be distinct from each other and from u, v, w (else an error). */
+int x3d_stats_update_uvw(x3d_backend *b, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                         x3d_real *const mean[9], x3d_real stat_inc);
+/* the species' share of update, :173-182: mean_phi, mean_phiphi <- phi, phi * phi; mean_phiphi = NULL: first moment only
+ * (the pressure mean of :162-170 would be such a call) */
+int x3d_stats_update_scalar(x3d_backend *b, const x3d_real *phi, x3d_real *mean_phi, x3d_real *mean_phiphi,
+                            x3d_real stat_inc);
+/* write_stats, :232-237: out = uprime, vprime, wprime = sqrt(max(0, uu - u^2)) ..., then uv - u v, uw - u w, vw - v w */
+int x3d_stats_derive(x3d_backend *b, x3d_real *const out[6], const x3d_real *const mean[9]);
+/* extension (the reference keeps 3-D means only): sums[m][q] (device, 9 * dims[dir_keep - 1] values, x3d_device_alloc) =
+ * the sum of moment m over the unpadded extent dims of the two directions other than dir_keep (1, 2 or 3), for every
+ * index q along dir_keep.  Deterministic: fixed-order partial sums in FP64 in both flavours, fixed-order second stage on
+ * the device, no atomics, one rounding at the store. */
+int x3d_stats_profile_sums(x3d_backend *b, const x3d_real *u, const x3d_real *v, const x3d_real *w, const int dims[3],
+                           int dir_keep, x3d_real *sums);
+/* prof[i] += (sums[i] * scale - prof[i]) * stat_inc, i < n (accumulate_mean, :61-70, on plane means): scale = 1 / points
+ * per plane over all ranks; a multi-rank caller all-reduces sums between the two calls */
+int x3d_stats_profile_accumulate(x3d_backend *b, x3d_real *prof, const x3d_real *sums, long n, x3d_real scale,
+                                 x3d_real stat_inc);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -229,6 +229,11 @@ PROTOTYPES = {
     "x3d_pfft_bwd_c_part": (I, [VP, VP, I]),
     "x3d_pfft_bwd_b_part": (I, [VP, VP, VP, I]),
     "x3d_pfft_bwd_a_part": (I, [VP, VP, VP, I]),
+    "x3d_stats_update_uvw": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), D]),
+    "x3d_stats_update_scalar": (I, [VP, VP, VP, VP, D]),
+    "x3d_stats_derive": (I, [VP, ctypes.POINTER(VP), ctypes.POINTER(VP)]),
+    "x3d_stats_profile_sums": (I, [VP, VP, VP, VP, c_int_p, I, VP]),
+    "x3d_stats_profile_accumulate": (I, [VP, VP, VP, ctypes.c_long, D, D]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),

@@ -976,6 +976,57 @@ class HipBackend:
         _lib.check(self.lib.x3d_field_volume_integral(self.h, f.ptr, self._dims(f.data_loc), ctypes.byref(out)))
         return self.comm.allreduce(out.value, "sum")
 
+    # ------------------------------------------------------------ flow statistics (csrc/stats.hip)
+    @staticmethod
+    def _need_vert(name, *fields):
+        """the reference's note, src/io/stats.f90:15-16: statistics are taken at VERT"""
+        for f in fields:
+            if f.data_loc != VERT:
+                raise X3dError(f"{name}: every field must be at VERT")
+
+    def stats_update_uvw(self, u, v, w, means, stat_inc):
+        """means[k] += (val_k - means[k]) * stat_inc for u, v, w, uu, vv, ww, uv, uw, vw in one launch
+        (stats_manager_t%update, src/io/stats.f90:143-159)"""
+        if len(means) != 9:
+            raise X3dError("stats_update_uvw: nine accumulators expected")
+        self._need_vert("stats_update_uvw", u, v, w, *means)
+        p = (VP * 9)(*[m.ptr for m in means])
+        _lib.check(self.lib.x3d_stats_update_uvw(self.h, u.ptr, v.ptr, w.ptr, p, float(stat_inc)))
+
+    def stats_update_scalar(self, phi, mean_phi, mean_phiphi, stat_inc):
+        """the same for one scalar and its square (src/io/stats.f90:173-182); mean_phiphi = None: first moment only"""
+        self._need_vert("stats_update_scalar", phi, mean_phi, *([] if mean_phiphi is None else [mean_phiphi]))
+        _lib.check(self.lib.x3d_stats_update_scalar(self.h, phi.ptr, mean_phi.ptr,
+                                                    None if mean_phiphi is None else mean_phiphi.ptr, float(stat_inc)))
+
+    def stats_derive(self, outs, means):
+        """outs = uprime, vprime, wprime, <u'v'>, <u'w'>, <v'w'> from the nine running means (src/io/stats.f90:232-237)"""
+        if len(outs) != 6 or len(means) != 9:
+            raise X3dError("stats_derive: six outputs and nine accumulators expected")
+        self._need_vert("stats_derive", *means)
+        po, pm = (VP * 6)(*[f.ptr for f in outs]), (VP * 9)(*[m.ptr for m in means])
+        _lib.check(self.lib.x3d_stats_derive(self.h, po, pm))
+        for f in outs:
+            f.set_data_loc(VERT)
+
+    def stats_profile_sums(self, u, v, w, dir_keep, sums):
+        """sums (device tensor of 9 * n_keep reals) <- the nine moments summed over this rank's share of the two
+        directions other than dir_keep; rank-local, no host synchronisation"""
+        self._need_vert("stats_profile_sums", u, v, w)
+        if dir_keep not in (DIR_X, DIR_Y, DIR_Z):
+            raise X3dError("stats_profile_sums: dir_keep must be 1, 2 or 3")
+        if sums.numel() < 9 * self.mesh.get_dims(VERT)[dir_keep - 1]:
+            raise X3dError("stats_profile_sums: sums holds fewer than 9 * n_keep values")
+        _lib.check(self.lib.x3d_stats_profile_sums(self.h, u.ptr, v.ptr, w.ptr, self._dims(VERT), int(dir_keep),
+                                                   sums.data_ptr()))
+
+    def stats_profile_accumulate(self, prof, sums, scale, stat_inc):
+        """prof += (sums * scale - prof) * stat_inc on two device tensors of equal size"""
+        if prof.numel() != sums.numel():
+            raise X3dError("stats_profile_accumulate: prof and sums differ in size")
+        _lib.check(self.lib.x3d_stats_profile_accumulate(self.h, prof.data_ptr(), sums.data_ptr(), prof.numel(),
+                                                         float(scale), float(stat_inc)))
+
     # ------------------------------------------------------------ faces
     def field_set_face(self, f, c_start, c_end, face):
         if f.dir != DIR_X:

@@ -47,6 +47,7 @@ class BaseCase:
     def __init__(self, solver):
         self.solver = solver
         self.monitoring = Monitoring(solver)
+        self.stats = None  # optional stats.Stats(solver, cfg): run() then samples and writes it (io_manager, base_case.f90:319-329)
         self.step_times = []
         self.initial_conditions()
 
@@ -151,13 +152,19 @@ class BaseCase:
         for it in range(start, n_iters + 1):
             t0 = time.perf_counter()
             output_due = s.n_output > 0 and it % s.n_output == 0
-            self.step(it, more=(it < n_iters and not output_due))
+            # a statistics sample reads the velocity like an output step does
+            sample_due = self.stats is not None and self.stats.cfg.sample_due(it)
+            self.step(it, more=(it < n_iters and not output_due and not sample_due))
             s.current_iter = it
+            if self.stats is not None:
+                self.stats.update(it)  # update_stats, base_case.f90:319
             if s.n_output > 0 and it % s.n_output == 0:
                 row = self.postprocess(it, it * s.dt)
                 if verbose and s.mesh.is_root():
                     print("time = %g iteration = %d enstrophy: %.13e div u max mean: %.3e %.3e"
                           % (row[0], it, row[1], row[2], row[3]))
+            if self.stats is not None:
+                self.stats.write(it)  # handle_io_step, base_case.f90:328
             s.backend.sync()
             self.step_times.append(time.perf_counter() - t0)
         s.flush_grad()

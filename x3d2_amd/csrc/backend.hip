@@ -119,6 +119,7 @@ extern "C" int x3d_backend_destroy(x3d_backend *b)
     hipFree(b->scratch[0]); hipFree(b->scratch[1]); hipFree(b->scratch[2]);
     x3d_prof_enable_c(b, 0);
     hipFree(b->red_buf); hipHostFree(b->red_host); hipFree(b->epi_dev);
+    if (b->stats_part) hipFree(b->stats_part);
     hipEventDestroy(b->ev0); hipEventDestroy(b->ev1);
     delete static_cast<std::unordered_set<const void *> *>(b->lds_optin);
     x3d_lazy_destroy(b);

@@ -159,6 +159,8 @@ struct x3d_backend {
     // profiles/r05_yslab_pipeline_timeline.txt).  With fewer workgroups than CUs some CUs stay empty and the exchange
     // starts at once; the kernels are memory-bound, 248 CUs stream what 256 do.  0 on one rank.
     int comm_reserve;
+    double *stats_part;  // partial sums of x3d_stats_profile_sums (stats.hip): FP64 in both flavours, grown on demand
+    long stats_cap;      // ... its size in doubles
 };
 // the RK / AB stage of one variable as the epilogue of a tile kernel (xscan.hip, k_ytile_transeq<EPI> / k_ytile_transeq3<EPI>):
 // d = x[ipend] + component;  [store: x[ipend] = d;]  y = base + sum_k c[k] (k == ipend ? d : x[k])

@@ -466,6 +466,19 @@ class Comm:
         dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
         return float(t.item())
 
+    def allreduce_tensor(self, t):
+        """sum of a small device tensor over all ranks, in place (the plane sums of the statistics' profile mode);
+        host-staged transport: through host memory"""
+        if self.size == 1:
+            return t
+        if self.backend == "nccl":
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            return t
+        h = t.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+        t.copy_(h)
+        return t
+
     def barrier(self):
         if self.size > 1:
             dist.barrier(group=self.group)
