@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -14,6 +14,13 @@ Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launc
 (456 B/DoF: what the entry points of the reference's backend interface cost), and the existing reduction
 x3d_scalar_product on the same field (16 B/DoF).  GB/s on those stated bytes; `ceiling` = fraction of the 6.2 TB/s copy
 ceiling (profiles/r04_copy_ceiling.txt).
+
+Family "ibm" (FP64, HIP-event time, median of --stat-iters): on a 512^3 periodic block with a cylinder of diameter
+L_x / 20 along z, (a) Ibm.body through the work list against one and three x3d_vecmult by a device mask; (b) the
+cylinder case's per-sub-step boundary path, x3d_outflow_params + x3d_cylinder_apply_bc + Ibm.body, against the calls
+of the reference composed (three slice_max_sum, three field_set_face_from_field, three vecmult), with the number of host
+waits for the stream in each (x3d_backend_counter 3); (c) make_cylinder((257, 128, 32)), 20 steps, ms per step with the
+work list and with X3D_NO_IBM_SPARSE=1.  `step_share` = fraction of the 40 ms of a 512^3 TGV step (README).
 """
 import argparse
 import json
@@ -91,18 +98,126 @@ def bench_stats(args):
         torch.cuda.empty_cache()
 
 
+def bench_ibm(args):
+    """one JSON line per measurement of the "ibm" family"""
+    import ctypes
+    from types import SimpleNamespace
+
+    import torch
+    from x3d2_amd import Mesh, _lib, make_cylinder
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.common import DIR_X, VERT, X_FACE
+    from x3d2_amd.ibm import Ibm, cylinder_mask
+    per = ("periodic",) * 2
+    n, twopi, step_ms = 512, 6.283185307179586, 40.0
+    mesh = Mesh((n, n, n), (1, 1, 1), (twopi,) * 3, per, per, per)
+    b = HipBackend(mesh)
+    al = b.allocator
+    u, v, w, iu, iv, iw, mask = (al.get_block(DIR_X, VERT) for _ in range(7))
+    rng = np.random.default_rng(0)
+    for f in (u, v, w):
+        b.set_field_data(f, 1.0 + 0.1 * rng.standard_normal((n, n, n), dtype=np.float32))
+    for f, c in ((iu, 1.0), (iv, 0.0), (iw, 0.0)):
+        f.fill(c)
+    ep1 = cylinder_mask(mesh, (twopi / 4, twopi / 2), twopi / 40)
+    mask.fill(1.0)
+    b.set_field_data(mask, ep1)
+    ibm = Ibm(SimpleNamespace(backend=b), ep1)
+    dx, gdt = twopi / n, 1e-3
+    rb = 4 if _lib.SINGLE else 8
+
+    def three_vecmult():
+        for f in (u, v, w):
+            b.vecmult(f, mask)
+
+    def new_path():
+        p = b.outflow_params(u, gdt, dx)
+        b.cylinder_apply_bc(u, v, w, iu, iv, iw, p)
+        ibm.body(u, v, w)
+
+    def composed_path():
+        uxmax, _ = b.slice_max_sum(u, n - 1)
+        _, s_in = b.slice_max_sum(u, 1)
+        _, s_out = b.slice_max_sum(u, n)
+        out_vel, frd = uxmax * gdt / dx, s_in / (n * n) - s_out / (n * n)
+        for f, st in ((u, iu), (v, iv), (w, iw)):
+            b.field_set_face_from_field(f, st, out_vel, X_FACE, flow_rate_diff=frd)
+        three_vecmult()
+
+    def timed(fn):
+        ms, times, walls = ctypes.c_float(), [], []
+        s0 = b.sync_count()
+        for i in range(args.stat_warmup + args.stat_iters):
+            b.sync()
+            t0 = time.perf_counter()
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            fn()
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times.append(ms.value)
+                walls.append((time.perf_counter() - t0) * 1e3)
+        syncs = (b.sync_count() - s0) / float(args.stat_warmup + args.stat_iters)
+        return float(np.median(times)), float(min(times)), float(np.median(walls)), syncs
+
+    res = {}
+    for name, fn in (("ibm.body (work list)", lambda: ibm.body(u, v, w)), ("one vecmult by a device mask", lambda: b.vecmult(u, mask)),
+                     ("three vecmult by a device mask", three_vecmult),
+                     ("boundary path: outflow_params + cylinder_apply_bc + ibm.body", new_path),
+                     ("boundary path composed: 3 slice_max_sum + 3 set_face_from_field + 3 vecmult", composed_path)):
+        t, tmin, wall, syncs = timed(fn)
+        res[name] = t
+        row = {"family": "ibm", "op": name, "n": n, "real_bytes": rb, "ms_median": t, "ms_min": tmin, "wall_ms_median": wall,
+               "launch_groups": args.stat_iters, "stream_syncs_per_call": syncs, "step_share": t / step_ms}
+        if name.startswith("ibm.body"):
+            row.update(n_segments=ibm.n_segments, n_masked=ibm.n_masked, masked_fraction=ibm.n_masked / float(n ** 3),
+                       bytes_moved=ibm.n_segments * 64 * rb * 7, bytes_of_one_vecmult=3 * rb * n ** 3)
+        if name.startswith("three"):
+            row["body_over_one_vecmult"] = res["ibm.body (work list)"] / res["one vecmult by a device mask"]
+            row["body_over_three_vecmult"] = res["ibm.body (work list)"] / t
+        if "composed" in name:
+            row["new_over_composed"] = res["boundary path: outflow_params + cylinder_apply_bc + ibm.body"] / t
+        print(json.dumps(row), flush=True)
+    del ibm, b, al, u, v, w, iu, iv, iw, mask
+    torch.cuda.empty_cache()
+    # the whole case, both forms from the same process, in this order
+    for dense in (False, True):
+        if dense:
+            os.environ["X3D_NO_IBM_SPARSE"] = "1"
+        else:
+            os.environ.pop("X3D_NO_IBM_SPARSE", None)
+        case = make_cylinder((257, 128, 32), fused=True)
+        sb = case.solver.backend
+        for it in range(1, 4):
+            case.step(it)
+        sb.sync()
+        t0 = time.perf_counter()
+        for it in range(4, 24):
+            case.step(it)
+        sb.sync()
+        t = (time.perf_counter() - t0) / 20 * 1e3
+        row = case.postprocess(23, 23 * case.solver.dt)
+        print(json.dumps({"family": "ibm", "op": "make_cylinder((257,128,32)), fused, AB3: 20 steps", "dense_mask": dense,
+                          "ms_per_step": t, "n_segments": case.solver.ibm.n_segments, "n_masked": case.solver.ibm.n_masked,
+                          "enstrophy": row[1], "div_u_max": row[2], "out_vel": case.out_vel}), flush=True)
+        del case, sb
+        torch.cuda.empty_cache()
+    os.environ.pop("X3D_NO_IBM_SPARSE", None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats"))
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm"))
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
     args = ap.parse_args()
     if args.family in ("all", "stats"):
         bench_stats(args)
-    if args.family == "stats":
+    if args.family in ("all", "ibm"):
+        bench_ibm(args)
+    if args.family in ("stats", "ibm"):
         return
     import torch
     from x3d2_amd import Mesh

@@ -653,6 +653,56 @@ module m_x3d2_hip_capi
       integer(c_long), value :: n
       real(x3d_creal), value :: scale, stat_inc
     end function
+    ! immersed boundary and the cylinder case (include/x3d2_hip.h, "immersed boundary"): ibm_t%body as one sparse launch,
+    ! compute_outflow_params / apply_BC_cylinder / the inlet plane of define_BC_cylinder without the host
+    integer(c_int) function x3d_ibm_create(b, ep1_host, dims, ibm) bind(C, name='x3d_ibm_create')
+      import :: c_ptr, c_int, x3d_creal
+      type(c_ptr), value :: b
+      real(x3d_creal), intent(in) :: ep1_host(*)
+      integer(c_int), intent(in) :: dims(3)
+      type(c_ptr), intent(out) :: ibm
+    end function
+    integer(c_int) function x3d_ibm_destroy(ibm) bind(C, name='x3d_ibm_destroy')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: ibm
+    end function
+    ! out = (listed segments, points with ep1 /= 1)
+    integer(c_int) function x3d_ibm_counts(ibm, out) bind(C, name='x3d_ibm_counts')
+      import :: c_ptr, c_int, c_long
+      type(c_ptr), value :: ibm
+      integer(c_long), intent(out) :: out(2)
+    end function
+    integer(c_int) function x3d_ibm_body(b, ibm, u, v, w, dims) bind(C, name='x3d_ibm_body')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: b, ibm, u, v, w
+      integer(c_int), intent(in) :: dims(3)
+    end function
+    ! params_dev: device address of (out_vel, flow_rate_diff)
+    integer(c_int) function x3d_outflow_params(b, u, dims, gdt, dx, params_dev) bind(C, name='x3d_outflow_params')
+      import :: c_ptr, c_int, x3d_creal
+      type(c_ptr), value :: b, u
+      integer(c_int), intent(in) :: dims(3)
+      real(x3d_creal), value :: gdt, dx
+      type(c_ptr), intent(out) :: params_dev
+    end function
+    integer(c_int) function x3d_outflow_params_get(b, out) bind(C, name='x3d_outflow_params_get')
+      import :: c_ptr, c_int, x3d_creal
+      type(c_ptr), value :: b
+      real(x3d_creal), intent(out) :: out(2)
+    end function
+    integer(c_int) function x3d_cylinder_apply_bc(b, u, v, w, in_u, in_v, in_w, dims, params_dev) &
+      bind(C, name='x3d_cylinder_apply_bc')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: b, u, v, w, in_u, in_v, in_w, params_dev
+      integer(c_int), intent(in) :: dims(3)
+    end function
+    integer(c_int) function x3d_inlet_noise(b, f, dims, base, amp, seed, draw) bind(C, name='x3d_inlet_noise')
+      import :: c_ptr, c_int, c_long_long, x3d_creal
+      type(c_ptr), value :: b, f
+      integer(c_int), intent(in) :: dims(3)
+      real(x3d_creal), value :: base, amp
+      integer(c_long_long), value :: seed, draw
+    end function
   end interface
 
 contains

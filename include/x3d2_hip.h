@@ -75,7 +75,9 @@ int x3d_backend_destroy(x3d_backend *b);
 int x3d_backend_create_like(x3d_backend **out, const x3d_backend *like, const int dims_vert[3]);
 /* diagnostics: which = 0 -> launches of the three-components-in-one transeq kernels since creation,
  * 1 -> those of them that also applied a pending velocity correction (x3d_transeq_x_update),
- * 2 -> launches of the single-pass HALO forms of the tile kernels (decomposed directions) */
+ * 2 -> launches of the single-pass HALO forms of the tile kernels (decomposed directions),
+ * 3 -> times an entry point made the host wait for the stream to hand a reduction's result over (the reductions,
+ *      x3d_slice_max_sum, x3d_outflow_params_get) */
 long x3d_backend_counter(const x3d_backend *b, int which);
 int x3d_backend_set_stream(x3d_backend *b, void *stream);
 /* round 5: CUs the persistent kernels (one workgroup per CU for a whole launch: the tile and scan kernels) leave FREE, so that
@@ -727,6 +729,39 @@ int x3d_stats_profile_sums(x3d_backend *b, const x3d_real *u, const x3d_real *v,
  * per plane over all ranks; a multi-rank caller all-reduces sums between the two calls */
 int x3d_stats_profile_accumulate(x3d_backend *b, x3d_real *prof, const x3d_real *sums, long n, x3d_real scale,
                                  x3d_real stat_inc);
+
+/* ---- immersed boundary and the cylinder case (csrc/ibm.hip): ibm_t, src/module/ibm.f90; case_cylinder_t,
+ * src/case/cylinder.f90.  None of the per-sub-step calls synchronises with the host. */
+typedef struct x3d_ibm x3d_ibm;
+/* ep1_host: the vertex mask [nz][ny][nx] (x fastest, unpadded; 1 in the fluid, 0 in the solid), read once.  The object
+ * keeps a work list of the 64-point-aligned x segments (i0, j, k) that hold a valid point with ep1 != 1, in ascending
+ * (k, j, i0) order, and the mask values of those segments -- no full-size device block.  A mask of ones: an empty list. */
+int x3d_ibm_create(x3d_backend *b, const x3d_real *ep1_host, const int dims[3], x3d_ibm **out);
+int x3d_ibm_destroy(x3d_ibm *ibm);
+/* out[0] = listed segments, out[1] = points with ep1 != 1 */
+int x3d_ibm_counts(const x3d_ibm *ibm, long out[2]);
+/* ibm_t%body, :148-170: u, v, w *= ep1 at the valid points of the listed segments, one launch, one wave per segment; the
+ * same bits as three x3d_vecmult by the mask (x * 1.0 = x).  Padding and points outside dims are never written; dims must
+ * be those of x3d_ibm_create.  An empty list returns without a launch. */
+int x3d_ibm_body(x3d_backend *b, const x3d_ibm *ibm, x3d_real *u, x3d_real *v, x3d_real *w, const int dims[3]);
+/* compute_outflow_params, src/case/cylinder.f90:109-147, on one rank and without the host: a launch over the planes
+ * i = 1, nx - 1, nx of u (FP64 partial sums in both flavours, fixed order, no atomics) and a one-workgroup finish leave
+ *   params[0] = out_vel = max(u[nx-1]) * gdt / dx,   params[1] = flow_rate_diff = (sum u[1] - sum u[nx]) / (ny * nz)
+ * in a device buffer the backend owns; *params_dev = its address, valid until the backend goes, rewritten by the next call. */
+int x3d_outflow_params(x3d_backend *b, const x3d_real *u, const int dims[3], x3d_real gdt, x3d_real dx,
+                       const x3d_real **params_dev);
+/* the two values of the last x3d_outflow_params on the host (waits for the stream): postprocess */
+int x3d_outflow_params_get(x3d_backend *b, x3d_real out[2]);
+/* apply_BC_cylinder, :226-243: three x3d_field_set_face_from_field(X_FACE) in one launch, c_end = params_dev[0] and
+ * flow_rate_diff = params_dev[1] read on the device: plane i = 1 of u, v, w from in_u, in_v, in_w;
+ * f[nx] = f[nx] - c_end * (f[nx] - f[nx-1]) + flow_rate_diff, the same order of operations. */
+int x3d_cylinder_apply_bc(x3d_backend *b, x3d_real *u, x3d_real *v, x3d_real *w, const x3d_real *in_u, const x3d_real *in_v,
+                          const x3d_real *in_w, const int dims[3], const x3d_real *params_dev);
+/* define_BC_cylinder, :200-210: plane i = 1 of f <- base + amp * (2 r - 1), r in [0, 1) generated like x3d_wall_noise's
+ * (splitmix64 of seed + draw, then of that key + k * ny + j; 53 bits); the rest of the block keeps its contents.
+ * FP64: values in [base - amp, base + amp); FP32: r is rounded to 24 bits and can be 1, the interval is closed. */
+int x3d_inlet_noise(x3d_backend *b, x3d_real *f, const int dims[3], x3d_real base, x3d_real amp, unsigned long long seed,
+                    unsigned long long draw);
 
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);

@@ -42,3 +42,25 @@ def make_channel(dims=(128, 65, 64), L=(4.0, 2.0, 2.0), stretching="top-bottom",
     solver = Solver(backend, mesh, SolverConfig(Re=Re, dt=dt, time_intg=time_intg, poisson_solver_type=poisson,
                                                  fused=fused, lowmem_transeq=lowmem_transeq))
     return ChannelCase(solver, ChannelConfig(**channel_kw))
+
+
+def make_cylinder(dims=(257, 128, 32), L=(20.0, 12.0, 6.0), Re=300.0, dt=0.0075, time_intg="AB3", poisson="FFT",
+                  fused=False, device=None, lazy=None, centre=None, radius=0.5, ep1=None, **cylinder_kw):
+    """cylinder set-up of examples/cylinder/input.x3d: Dirichlet ends in x (inflow / convective outflow), periodic
+    y and z, AB3, immersed boundary on; cylinder_kw -> CylinderConfig (init_noise, inlet_noise, seed).  One rank.
+
+    The reference reads its body from a file written by an outside tool.  The default here is this project's own choice:
+    a circular cylinder of diameter 1 (radius 0.5) along z through (L_x / 4, L_y / 2).  centre / radius change it,
+    ep1 (numpy [nz, ny, nx]) replaces it by any mask."""
+    from .backend import HipBackend
+    from .case import CylinderCase, CylinderConfig
+    from .ibm import Ibm, cylinder_mask
+    from .solver import Solver, SolverConfig
+    mesh = Mesh(tuple(dims), (1, 1, 1), tuple(L), ("dirichlet",) * 2, ("periodic",) * 2, ("periodic",) * 2)
+    backend = HipBackend(mesh, device=device, lazy=lazy)
+    solver = Solver(backend, mesh, SolverConfig(Re=Re, dt=dt, time_intg=time_intg, poisson_solver_type=poisson,
+                                                 fused=fused, ibm_on=True))
+    if ep1 is None:
+        ep1 = cylinder_mask(mesh, (L[0] / 4.0, L[1] / 2.0) if centre is None else centre, radius, axis=2)
+    solver.ibm = Ibm(solver, ep1)
+    return CylinderCase(solver, CylinderConfig(**cylinder_kw))

@@ -234,6 +234,14 @@ PROTOTYPES = {
     "x3d_stats_derive": (I, [VP, ctypes.POINTER(VP), ctypes.POINTER(VP)]),
     "x3d_stats_profile_sums": (I, [VP, VP, VP, VP, c_int_p, I, VP]),
     "x3d_stats_profile_accumulate": (I, [VP, VP, VP, ctypes.c_long, D, D]),
+    "x3d_ibm_create": (I, [VP, c_double_p, c_int_p, ctypes.POINTER(VP)]),
+    "x3d_ibm_destroy": (I, [VP]),
+    "x3d_ibm_counts": (I, [VP, ctypes.POINTER(ctypes.c_long)]),
+    "x3d_ibm_body": (I, [VP, VP, VP, VP, VP, c_int_p]),
+    "x3d_outflow_params": (I, [VP, VP, c_int_p, D, D, ctypes.POINTER(VP)]),
+    "x3d_outflow_params_get": (I, [VP, c_double_p]),
+    "x3d_cylinder_apply_bc": (I, [VP, VP, VP, VP, VP, VP, VP, c_int_p, VP]),
+    "x3d_inlet_noise": (I, [VP, VP, c_int_p, D, D, ctypes.c_ulonglong, ctypes.c_ulonglong]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),

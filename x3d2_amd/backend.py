@@ -1027,6 +1027,42 @@ class HipBackend:
         _lib.check(self.lib.x3d_stats_profile_accumulate(self.h, prof.data_ptr(), sums.data_ptr(), prof.numel(),
                                                          float(scale), float(stat_inc)))
 
+    # ------------------------------------------------------------ immersed boundary / cylinder case (csrc/ibm.hip)
+    def sync_count(self):
+        """how often a library call made the host wait for the stream to fetch a reduction's result"""
+        return int(self.lib.x3d_backend_counter(self.h, 3))
+
+    def outflow_params(self, u, gdt, dx):
+        """compute_outflow_params (src/case/cylinder.f90:109-147) without the host: the device address of
+        {out_vel, flow_rate_diff}, valid until the next call"""
+        if u.dir != DIR_X or u.data_loc == NULL_LOC:
+            raise X3dError("outflow_params: a DIR_X field with a valid data_loc is needed")
+        if self.comm.size > 1:
+            raise X3dError("outflow_params: one rank only (the plane reductions are rank-local)")
+        out = VP()
+        _lib.check(self.lib.x3d_outflow_params(self.h, u.ptr, self._dims(u.data_loc), float(gdt), float(dx),
+                                               ctypes.byref(out)))
+        return out
+
+    def outflow_params_get(self):
+        """(out_vel, flow_rate_diff) of the last outflow_params, on the host"""
+        out = (_lib.REAL * 2)()
+        _lib.check(self.lib.x3d_outflow_params_get(self.h, out))
+        return float(out[0]), float(out[1])
+
+    def cylinder_apply_bc(self, u, v, w, in_u, in_v, in_w, params):
+        """apply_BC_cylinder (:226-243) in one launch; params: the device scalars of outflow_params"""
+        for f in (u, v, w):
+            if f.dir != DIR_X or f.data_loc == NULL_LOC:
+                raise X3dError("cylinder_apply_bc: DIR_X fields with a valid data_loc are needed")
+        _lib.check(self.lib.x3d_cylinder_apply_bc(self.h, u.ptr, v.ptr, w.ptr, in_u.ptr, in_v.ptr, in_w.ptr,
+                                                  self._dims(u.data_loc), params))
+
+    def inlet_noise(self, f, base, amp, seed, draw):
+        """plane x = 1 of the (VERT) inlet field f <- base + amp * (2 r - 1), generated on the device"""
+        _lib.check(self.lib.x3d_inlet_noise(self.h, f.ptr, self._dims(VERT), float(base), float(amp),
+                                            int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)))
+
     # ------------------------------------------------------------ faces
     def field_set_face(self, f, c_start, c_end, face):
         if f.dir != DIR_X:

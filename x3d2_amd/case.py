@@ -1,12 +1,13 @@
 """Flow cases: mirror of base_case_t%run (/root/reference/src/case/base_case.f90:181-353),
-the TGV case (src/case/tgv.f90) and the monitoring series
+the TGV case (src/case/tgv.f90), the channel (src/case/channel.f90), the cylinder (src/case/cylinder.f90) and the
+monitoring series
 (src/postprocess/monitoring.f90:46-90)."""
 import os
 import time
 
 import numpy as np
 
-from .common import BC_DIRICHLET, CELL, DIR_X, DIR_Z, VERT, Y_FACE
+from .common import BC_DIRICHLET, CELL, DIR_X, DIR_Z, VERT, Y_FACE, X3dError
 
 
 class Monitoring:
@@ -101,6 +102,11 @@ class BaseCase:
         walls = self.deferred_walls() if s.fused and os.environ.get("X3D_NO_DEFER_WALLS") != "1" else None
         defer_upd = (s.fused and (type(self).apply_BC is BaseCase.apply_BC or walls is not None)
                      and os.environ.get("X3D_NO_DEFER") != "1" and s.time_integrator.sname.upper().startswith("RK"))
+        ibm = s.ibm
+        if ibm is not None:
+            # ibm%body masks the COMPLETED velocity with the BCs already stamped (base_case.f90:281-285): the new velocity
+            # cannot be formed inside the pressure correction's first kernels then -- the explicit order
+            walls, defer_upd = None, False
         if s.fused and self.forcings_idle(it):
             # nothing touches the derivatives between transeq and the RK / AB stage: the last accumulation of
             # transeq may be folded into the stage's linear combination (Solver.transeq_fused)
@@ -123,6 +129,8 @@ class BaseCase:
             s.pending_walls = walls  # apply_BC happens inside the pressure correction's first kernels
         else:
             self.apply_BC(s.u, s.v, s.w)
+        if ibm is not None:
+            ibm.body(s.u, s.v, s.w)
         # not the last sub-step of the step and no hook looks at the velocity before the next transeq: its
         # pressure-gradient correction can wait for that kernel (Solver.transeq_fused)
         defer_grad = not last and s.fused and self.correction_deferrable()
@@ -302,3 +310,81 @@ class ChannelCase(BaseCase):
         b = self.solver.backend
         for f, st in zip((u, v, w), self.bc_start_y):
             b.field_set_face_from_field(f, st, 0.0, Y_FACE)
+
+
+class CylinderConfig:
+    """cylinder_config_t, src/config.f90:56-61, 251-286 (namelist cylinder_nml)"""
+
+    def __init__(self, init_noise=(0.0, 0.0, 0.0), inlet_noise=(0.0, 0.0, 0.0), seed=None):
+        self.init_noise, self.inlet_noise = tuple(float(n) for n in init_noise), tuple(float(n) for n in inlet_noise)
+        self.seed = seed  # the reference draws unseeded random_number; a seed makes runs repeatable
+
+
+class CylinderCase(BaseCase):
+    """src/case/cylinder.f90: uniform inflow u = 1 at x = 0, convective outflow at x = L_x, the body through the
+    solver's immersed boundary (solver.ibm).
+
+    The reference takes three slice reductions through the host, rebuilds the inlet profile there and uploads three
+    full blocks per sub-step (:129-134, 192-218), then stamps the faces with three launches (:231-242).  Here the two
+    outflow parameters stay on the device (x3d_outflow_params), the inlet fields are filled once when inlet_noise = 0
+    (the example's setting) and regenerated in place otherwise (x3d_inlet_noise), and apply_BC is one launch that
+    reads the parameters where they are (x3d_cylinder_apply_bc).  No call of a sub-step waits for the host.
+
+    One rank: the non-periodic Poisson solve is not built for a decomposed mesh."""
+
+    def __init__(self, solver, cylinder_cfg=None):
+        self.cylinder_cfg = cylinder_cfg or CylinderConfig()
+        seed = self.cylinder_cfg.seed
+        self.rng = np.random.default_rng(seed)  # initial condition (host, once)
+        self.noise_seed = int(seed) if seed is not None else int(np.random.SeedSequence().entropy) & (2 ** 63 - 1)
+        self.noise_draws = 0
+        self.bc_start_x = None   # bc_start_u_x / v_x / w_x: the inlet fields
+        self.params = None       # device address of {out_vel, flow_rate_diff}
+        self.out_vel = self.flow_rate_diff = 0.0
+        self.outflow_rows = []   # (t, out_vel, flow_rate_diff) next to monitoring.rows
+        if solver.backend.comm.size > 1:
+            raise X3dError("CylinderCase: one rank only")
+        super().__init__(solver)
+
+    def initial_conditions(self):  # :56-102
+        s, m = self.solver, self.solver.mesh
+        nx, ny, nz = m.get_dims(VERT)
+        x = m.vert_coords[0][None, None, :] - m.L[0] / 2.0
+        um = np.exp(-0.2 * x * x)
+        shape = (nz, ny, nx)
+        noise = self.cylinder_cfg.init_noise
+        for f, base, n in zip((s.u, s.v, s.w), (1.0, 0.0, 0.0), noise):
+            r = self.rng.random(shape) if n != 0.0 else 0.5
+            f.set_data_loc(VERT)
+            s.backend.set_field_data(f, base + n * um * (2 * r - 1.0) * np.ones(shape))
+
+    def define_BC(self):  # :159-219
+        s, b = self.solver, self.solver.backend
+        # Two quirks of the reference are kept.  (1) define_BC runs BEFORE this sub-step's integrator stage, so gdt is
+        # the previous stage's -- and 0.0 on the very first sub-step (time_integrator.f90 initialises it so): out_vel is
+        # then 0 and the first outflow stamp only adds flow_rate_diff.  (2) flow_rate_diff divides by THIS rank's
+        # ny * nz (:124-126), not the global plane.
+        self.params = b.outflow_params(s.u, s.time_integrator.gdt, float(s.mesh.d[0]))
+        noise = self.cylinder_cfg.inlet_noise
+        first = self.bc_start_x is None
+        if first:
+            self.bc_start_x = [b.allocator.get_block(DIR_X, VERT) for _ in range(3)]
+            for f, base in zip(self.bc_start_x, (1.0, 0.0, 0.0)):
+                f.set_data_loc(VERT)
+                f.fill(base)  # (only the plane x = 1 is ever read)
+        if any(n != 0.0 for n in noise):
+            half_L = float(s.mesh.L[0]) / 2.0
+            um = float(np.exp(-0.2 * half_L * half_L))  # :169-170, folded into the amplitude
+            for c, (f, base, n) in enumerate(zip(self.bc_start_x, (1.0, 0.0, 0.0), noise)):
+                b.inlet_noise(f, base, n * um, self.noise_seed, 3 * self.noise_draws + c)
+            self.noise_draws += 1
+
+    def apply_BC(self, u, v, w):  # :226-243
+        fu, fv, fw = self.bc_start_x
+        self.solver.backend.cylinder_apply_bc(u, v, w, fu, fv, fw, self.params)
+
+    def postprocess(self, it, t):  # :258-274
+        if self.params is not None:
+            self.out_vel, self.flow_rate_diff = self.solver.backend.outflow_params_get()
+        self.outflow_rows.append((t, self.out_vel, self.flow_rate_diff))
+        return super().postprocess(it, t)

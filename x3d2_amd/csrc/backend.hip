@@ -120,6 +120,8 @@ extern "C" int x3d_backend_destroy(x3d_backend *b)
     x3d_prof_enable_c(b, 0);
     hipFree(b->red_buf); hipHostFree(b->red_host); hipFree(b->epi_dev);
     if (b->stats_part) hipFree(b->stats_part);
+    if (b->bc_params) hipFree(b->bc_params);
+    if (b->bc_part) hipFree(b->bc_part);
     hipEventDestroy(b->ev0); hipEventDestroy(b->ev1);
     delete static_cast<std::unordered_set<const void *> *>(b->lds_optin);
     x3d_lazy_destroy(b);
@@ -142,7 +144,7 @@ extern "C" long x3d_backend_counter(const x3d_backend *b, int which)
 {
     X3D_RANGE(__func__);
     if (!b) return -1;
-    return which == 0 ? b->n_tq3 : (which == 1 ? b->n_upd : (which == 2 ? b->n_halo : -1));
+    return which == 0 ? b->n_tq3 : (which == 1 ? b->n_upd : (which == 2 ? b->n_halo : (which == 3 ? b->n_sync : -1)));
 }
 
 extern "C" int x3d_backend_set_stream(x3d_backend *b, void *stream)
@@ -716,6 +718,7 @@ static int run_reduce(x3d_backend *b, const real_t *x, const real_t *y, const in
     X3D_HIP(hipMemcpyAsync(b->red_host, b->red_buf, sizeof(real_t) * 2 * b->red_cap, hipMemcpyDeviceToHost,
                            b->stream));
     X3D_HIP(hipStreamSynchronize(b->stream));
+    b->n_sync++;
     real_t s = 0.0, m = 0.0;
     for (int i = 0; i < grid; i++) {
         s += b->red_host[i];
@@ -862,15 +865,7 @@ extern "C" int x3d_field_shift_to_mean(x3d_backend *b, real_t *f, const int dims
     return shift_by_impl(b, f, shift);
 }
 
-// splitmix64 of (seed, counter): the value depends on its inputs only, not on the launch geometry
-__host__ __device__ inline unsigned long long x3d_mix64(unsigned long long z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
+// (x3d_mix64: common.h)
 // planes y = 1 and y = ny of f <- amp * (2 r - 1), r uniform in [0, 1) with 53 random bits:
 // r(face, i, k) = mix64(mix64(seed + draw) + (face * nz + k) * nx + i) >> 11) * 2^-53
 __global__ void __launch_bounds__(256) k_wall_noise(real_t *__restrict__ f, int nx, int ny, int nz, long nxp, long nyp,
@@ -950,6 +945,7 @@ extern "C" int x3d_slice_max_sum(x3d_backend *b, const real_t *f, const int dims
     X3D_HIP(hipMemcpyAsync(b->red_host, b->red_buf, sizeof(real_t) * 2 * b->red_cap, hipMemcpyDeviceToHost,
                            b->stream));
     X3D_HIP(hipStreamSynchronize(b->stream));
+    b->n_sync++;
     real_t s = 0.0, m = -HUGE_VAL;
     for (int i = 0; i < grid; i++) {
         s += b->red_host[i];

@@ -115,6 +115,15 @@ __device__ __forceinline__ void vmcnt_pad_stores()
     for (int k = 0; k < N; k++) __builtin_nontemporal_store(0.0f, &g_vmcnt_sink[k * 1024 + (threadIdx.x & 1023)]);
 }
 
+// splitmix64 of (seed, counter): the value depends on its inputs only, not on the launch geometry
+__host__ __device__ static inline unsigned long long x3d_mix64(unsigned long long z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // Pencil enumeration for one direction of the Cartesian-pitched block:
 // pencil p -> base = (p % dim0) * s0 + (p / dim0) * s1, rows advance by rs.
 struct PencilGeom {
@@ -161,7 +170,11 @@ struct x3d_backend {
     int comm_reserve;
     double *stats_part;  // partial sums of x3d_stats_profile_sums (stats.hip): FP64 in both flavours, grown on demand
     long stats_cap;      // ... its size in doubles
+    real_t *bc_params;   // {out_vel, flow_rate_diff} of x3d_outflow_params (ibm.hip): read by x3d_cylinder_apply_bc on the device
+    double *bc_part;     // ... its stage-1 partials, [X3D_BC_PARTS][3] = sum u[1], sum u[nx], max u[nx-1]
+    long n_sync;         // host waits for the stream inside the reductions and x3d_outflow_params_get (x3d_backend_counter 3)
 };
+#define X3D_BC_PARTS 1024
 // the RK / AB stage of one variable as the epilogue of a tile kernel (xscan.hip, k_ytile_transeq<EPI> / k_ytile_transeq3<EPI>):
 // d = x[ipend] + component;  [store: x[ipend] = d;]  y = base + sum_k c[k] (k == ipend ? d : x[k])
 struct TileEpi {

@@ -16,7 +16,8 @@ class SolverConfig:
 
     def __init__(self, Re=1600.0, dt=1e-3, n_iters=10, n_output=0, time_intg="RK3", poisson_solver_type="FFT",
                  der1st_scheme="compact6", der2nd_scheme="compact6", interpl_scheme="classic",
-                 stagder_scheme="compact6", lowmem_transeq=False, fused=False, n_species=0, pr_species=None):
+                 stagder_scheme="compact6", lowmem_transeq=False, fused=False, n_species=0, pr_species=None,
+                 ibm_on=False):
         self.Re, self.dt, self.n_iters, self.n_output = Re, dt, n_iters, n_output
         self.time_intg, self.poisson_solver_type = time_intg, poisson_solver_type
         self.der1st_scheme, self.der2nd_scheme = der1st_scheme, der2nd_scheme
@@ -29,6 +30,9 @@ class SolverConfig:
         # fused = True : same arithmetic with reorders / sums / axpy chains folded
         #                into the kernels
         self.fused = fused
+        # ibm_on (src/config.f90, solver_params): the run carries an immersed boundary; whoever builds the case attaches it
+        # (solver.ibm = Ibm(solver, ep1) or Ibm.from_file(solver, path); make_cylinder does)
+        self.ibm_on = bool(ibm_on)
 
 
 def allocate_tdsops(dirps, backend, mesh, der1st_scheme, der2nd_scheme, interpl_scheme, stagder_scheme):
@@ -135,6 +139,8 @@ class Solver:
             self.transeq = self.transeq_lowmem if self.lowmem_transeq else self.transeq_default
         if self.fused:
             self.pressure_correction = self.pressure_correction_fused
+        # solver%ibm (src/solver.f90, ibm_on): None = no immersed boundary, and BaseCase.substep is what it was
+        self.ibm = None
 
     # ---- src/solver.f90:291-389
     def transeq_default(self, rhs, variables):
