@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -21,6 +21,13 @@ cylinder case's per-sub-step boundary path, x3d_outflow_params + x3d_cylinder_ap
 of the reference composed (three slice_max_sum, three field_set_face_from_field, three vecmult), with the number of host
 waits for the stream in each (x3d_backend_counter 3); (c) make_cylinder((257, 128, 32)), 20 steps, ms per step with the
 work list and with X3D_NO_IBM_SPARSE=1.  `step_share` = fraction of the 40 ms of a 512^3 TGV step (README).
+
+Family "snapshot" (FP64, --snap-n^3 = 512^3, median of --stat-iters; not part of "all"): (a) the pack kernel with six
+variables (u, v, w, p, vort, qcrit) at strides (1,1,1) and (2,2,2), 4- and 8-byte output: HIP-event ms and GB/s on
+touched source lines plus output bytes (a 128-byte line counts whole when one of its points is kept), next to the
+6.2 TB/s copy ceiling; (b) host-visible time of Snapshots.write from call to return against the composed path in the
+same process (six get_field_data, two compute_*, numpy striding and astype); (c) a 20-step TGV run at snapshot_freq = 5
+against the same run without snapshots: added wall time per snapshot.
 """
 import argparse
 import json
@@ -204,12 +211,134 @@ def bench_ibm(args):
     os.environ.pop("X3D_NO_IBM_SPARSE", None)
 
 
+def bench_snapshot(args):
+    """one JSON line per measurement of the "snapshot" family"""
+    import ctypes
+    import tempfile
+
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.common import DIR_X, DIR_Y, DIR_Z, VERT
+    from x3d2_amd.snapshot import SnapshotConfig, Snapshots
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    fields = ("pressure", "vorticity", "qcriterion")
+    tmp = tempfile.mkdtemp(prefix="x3d_snap_")
+    case = make_tgv(n, fused=True)
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    s.keep_pressure = True
+    case.step(1, want_pressure=True)
+    s.flush_grad()
+    nxp = b.padded_dims[0]
+
+    def grads():
+        g = []
+        for f in (s.u, s.v, s.w):
+            for dirps, d in ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z)):
+                o = al.get_block(DIR_X, VERT)
+                b.tds_apply(o, f, dirps.der1st, d)
+                g.append(o)
+        return g
+
+    # (a) the pack kernel alone
+    g = grads()
+    pv = al.get_block(DIR_X, VERT)
+    b.tds_apply(pv, s.pressure, s.zdirps.interpl_p2v, DIR_Z)
+    variables = [("copy", s.u, 1.0), ("copy", s.v, 1.0), ("copy", s.w, 1.0), ("copy", pv, 1.0 / s.dt), ("vort", g), ("qcrit", g)]
+    for stride in ((1, 1, 1), (2, 2, 2)):
+        cnt = tuple((n + st - 1) // st for st in stride)
+        for dt in (np.float32, np.float64):
+            size = np.dtype(dt).itemsize
+            out = torch.empty(6 * cnt[0] * cnt[1] * cnt[2] * size, dtype=torch.uint8, device=b.device)
+            ms, times = ctypes.c_float(), []
+            for i in range(args.stat_warmup + args.stat_iters):
+                _lib.check(b.lib.x3d_timer_start(b.h))
+                b.snapshot_pack(variables, (0, 0, 0), stride, cnt, out, dt)
+                _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+                if i >= args.stat_warmup:
+                    times.append(ms.value)
+            t = float(np.median(times))
+            row_bytes = n * rb if stride[0] * rb < 128 else cnt[0] * 128  # (kept rows only; every line of a kept row)
+            src = (4 + 18) * cnt[1] * cnt[2] * row_bytes  # four COPY sources, nine gradient blocks read by each of vort, qcrit
+            total = src + out.numel()
+            print(json.dumps({"family": "snapshot", "op": "pack, six variables", "n": n, "stride": stride, "out_bytes": size,
+                              "real_bytes": rb, "ms_median": t, "ms_min": float(min(times)), "launches": len(times),
+                              "source_bytes": src, "output_bytes": out.numel(), "GBs": total / t / 1e6,
+                              "ceiling": total / t / 1e6 / 6200.0, "row_pitch": nxp}), flush=True)
+            del out
+    for f in g + [pv]:
+        al.release_block(f)
+
+    # (b) host-visible cost of Snapshots.write against the composed path
+    stride = (2, 2, 2)
+    snap = Snapshots(s, SnapshotConfig(snapshot_freq=1, snapshot_prefix=os.path.join(tmp, "b"), output_stride=stride,
+                                       snapshot_sp=True, output_fields=fields))
+
+    def composed():
+        gg = grads()
+        o = al.get_block(DIR_X, VERT)
+        res = []
+        for fn in (b.compute_vorticity, b.compute_qcriterion):
+            fn(o, *gg)
+            o.set_data_loc(VERT)
+            res.append(b.get_field_data(o)[::2, ::2, ::2].astype(np.float32))
+        for f in (s.u, s.v, s.w):
+            res.append(b.get_field_data(f)[::2, ::2, ::2].astype(np.float32))
+        t1, t2 = al.get_block(DIR_X, VERT), al.get_block(DIR_X, VERT)
+        b.tds_apply(t1, s.pressure, s.zdirps.interpl_p2v, DIR_Z)
+        b.tds_apply(t2, t1, s.ydirps.interpl_p2v, DIR_Y)
+        b.tds_apply(t1, t2, s.xdirps.interpl_p2v, DIR_X)
+        t1.set_data_loc(VERT)
+        res.append((b.get_field_data(t1) * (1.0 / s.dt))[::2, ::2, ::2].astype(np.float32))
+        for f in gg + [o, t1, t2]:
+            al.release_block(f)
+        return res
+
+    for name, fn, after in (("Snapshots.write, call to return", lambda it: snap.write(it), snap.finalise),
+                            ("composed: 6 get_field_data + 2 compute_* + numpy stride / astype", lambda it: composed(), None)):
+        walls, s0 = [], b.sync_count()
+        for i in range(3 + 10):
+            b.sync()
+            t0 = time.perf_counter()
+            fn(i + 1)
+            w = (time.perf_counter() - t0) * 1e3
+            if after is not None:
+                after()  # (outside the timed region: the files are written, both buffers are free again)
+            if i >= 3:
+                walls.append(w)
+        print(json.dumps({"family": "snapshot", "op": name, "n": n, "stride": stride, "out_bytes": 4,
+                          "wall_ms_median": float(np.median(walls)), "wall_ms_min": float(min(walls)), "calls": len(walls),
+                          "stream_syncs": b.sync_count() - s0}), flush=True)
+    del snap, case, s, b, al
+    torch.cuda.empty_cache()
+
+    # (c) a 20-step run with and without snapshots
+    res = {}
+    for with_snap in (False, True):
+        case = make_tgv(n, fused=True)
+        if with_snap:
+            case.snapshots = Snapshots(case.solver, SnapshotConfig(snapshot_freq=5, snapshot_prefix=os.path.join(tmp, "c"),
+                                                                   output_stride=stride, snapshot_sp=True, output_fields=fields))
+        case.run(n_iters=3)
+        case.solver.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        case.solver.backend.sync()
+        res[with_snap] = (time.perf_counter() - t0) * 1e3
+        del case
+        torch.cuda.empty_cache()
+    print(json.dumps({"family": "snapshot", "op": "TGV, fused, RK3: 20 steps, snapshot_freq 5", "n": n, "stride": stride,
+                      "out_bytes": 4, "wall_ms_without": res[False], "wall_ms_with": res[True], "snapshots": 4,
+                      "added_ms_per_snapshot": (res[True] - res[False]) / 4.0}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm"))
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot"))
+    ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
     args = ap.parse_args()
@@ -217,7 +346,9 @@ def main():
         bench_stats(args)
     if args.family in ("all", "ibm"):
         bench_ibm(args)
-    if args.family in ("stats", "ibm"):
+    if args.family == "snapshot":
+        bench_snapshot(args)
+    if args.family in ("stats", "ibm", "snapshot"):
         return
     import torch
     from x3d2_amd import Mesh

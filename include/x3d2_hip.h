@@ -763,6 +763,37 @@ int x3d_cylinder_apply_bc(x3d_backend *b, x3d_real *u, x3d_real *v, x3d_real *w,
 int x3d_inlet_noise(x3d_backend *b, x3d_real *f, const int dims[3], x3d_real base, x3d_real amp, unsigned long long seed,
                     unsigned long long draw);
 
+/* ---- snapshots (csrc/snapshot.hip): the device side of snapshot_manager_t%write_fields (src/io/snapshot_manager.f90:287-340)
+ * and stride_data_to_buffer (src/io/io_field_utils.f90:75-124).  The reference copies every field to the host whole and
+ * strides it there; vort and qcrit first fill two full blocks (src/postprocess/postprocess.f90, compute_derived_fields).
+ * Here one launch packs every variable of a snapshot, decimated and converted, and one asynchronous copy moves the result. */
+enum { X3D_SNAP_COPY = 0, X3D_SNAP_VORT = 1, X3D_SNAP_QCRIT = 2 };
+#define X3D_SNAP_MAXVAR 16
+/* one output variable.  COPY: src[0] * scale, rounded once in the real kind, then converted to the output type (scale = 1:
+ * the source's bits).  VORT / QCRIT: src[0..8] = dudx, dudy, dudz, dvdx, dvdy, dvdz, dwdx, dwdy, dwdz; the formulas of
+ * x3d_compute_vorticity / x3d_compute_qcriterion (src/backend/omp/backend.f90:616-649) at the kept points; scale unused. */
+typedef struct x3d_snapshot_var {
+    int kind;
+    x3d_real scale;
+    const x3d_real *src[9];
+} x3d_snapshot_var;
+/* out[v][kz][ky][kx] (dense, x fastest, no padding; out_bytes = 4 or 8: float or double, whatever the real kind) =
+ * variable v at the local vertex (first[0] + kx * stride[0], first[1] + ky * stride[1], first[2] + kz * stride[2]),
+ * kx < count[0] ...; every kept index must lie inside dims (else an error, nothing is launched).  Source blocks carry the
+ * blocks' row padding.  If a copy of `out` started by x3d_snapshot_copy_async is still in flight the launch waits for it on
+ * the device.  No host synchronisation. */
+int x3d_snapshot_pack(x3d_backend *b, const x3d_snapshot_var *vars, int nvar, const int dims[3], const int first[3],
+                      const int stride[3], const int count[3], int out_bytes, void *out);
+/* nbytes of the packed device buffer `dev` to pinned host memory, ordered behind everything queued on the backend's stream
+ * by an event, on copy_stream (NULL, or the backend's own stream: a stream the backend creates at first use and owns);
+ * a second event is recorded behind the copy.  *handle names that event until the next copy of the same `dev`.  Returns at
+ * once; the backend's stream never waits for the copy. */
+int x3d_snapshot_copy_async(x3d_backend *b, void *host_pinned, const void *dev, long nbytes, void *copy_stream, int *handle);
+/* *done = 1 if the copy behind `handle` has completed, else 0; never blocks */
+int x3d_snapshot_done(x3d_backend *b, int handle, int *done);
+/* blocks the host until it has; counted by x3d_backend_counter(b, 3) */
+int x3d_snapshot_wait(x3d_backend *b, int handle);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

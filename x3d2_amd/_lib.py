@@ -242,6 +242,10 @@ PROTOTYPES = {
     "x3d_outflow_params_get": (I, [VP, c_double_p]),
     "x3d_cylinder_apply_bc": (I, [VP, VP, VP, VP, VP, VP, VP, c_int_p, VP]),
     "x3d_inlet_noise": (I, [VP, VP, c_int_p, D, D, ctypes.c_ulonglong, ctypes.c_ulonglong]),
+    "x3d_snapshot_pack": (I, [VP, VP, I, c_int_p, c_int_p, c_int_p, c_int_p, I, VP]),
+    "x3d_snapshot_copy_async": (I, [VP, VP, VP, ctypes.c_long, VP, c_int_p]),
+    "x3d_snapshot_done": (I, [VP, I, c_int_p]),
+    "x3d_snapshot_wait": (I, [VP, I]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),
@@ -249,6 +253,13 @@ PROTOTYPES = {
     "x3d_prof_reset": (I, [VP]),
     "x3d_prof_get": (I, [VP, I, I, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double)]),
 }
+
+
+
+class SnapshotVar(ctypes.Structure):
+    """x3d_snapshot_var of include/x3d2_hip.h"""
+    _fields_ = [("kind", I), ("scale", REAL), ("src", VP * 9)]
+
 
 _lib = None
 

@@ -1063,6 +1063,65 @@ class HipBackend:
         _lib.check(self.lib.x3d_inlet_noise(self.h, f.ptr, self._dims(VERT), float(base), float(amp),
                                             int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)))
 
+    # ------------------------------------------------------------ snapshots (csrc/snapshot.hip)
+    SNAP_KINDS = {"copy": 0, "vort": 1, "qcrit": 2}
+
+    def snapshot_pack(self, variables, first, stride, count, out, out_dtype):
+        """one launch for a whole snapshot: out (a device tensor, filled densely as [variable][kz][ky][kx] in out_dtype =
+        float32 or float64) <- the variables at the local vertices first + k * stride, k < count per direction.
+        variables: ("copy", field, scale) | ("vort", nine gradient fields) | ("qcrit", nine gradient fields), the
+        gradients in compute_vorticity's order.  Returns the bytes written.  No host synchronisation."""
+        n = len(variables)
+        if not 1 <= n <= 16:
+            raise X3dError("snapshot_pack: 1 .. 16 variables")
+        tab = (_lib.SnapshotVar * n)()
+        for d, var in zip(tab, variables):
+            kind = var[0]
+            if kind not in self.SNAP_KINDS:
+                raise X3dError(f"snapshot_pack: unknown kind {kind!r}")
+            d.kind = self.SNAP_KINDS[kind]
+            if kind == "copy":
+                fields, d.scale = [var[1]], float(var[2])
+            else:
+                fields, d.scale = list(var[1]), 1.0
+                if len(fields) != 9:
+                    raise X3dError("snapshot_pack: nine gradient fields expected")
+            for m, f in enumerate(fields):
+                d.src[m] = f.ptr
+        size = np.dtype(out_dtype).itemsize
+        if np.dtype(out_dtype) not in (np.dtype("float32"), np.dtype("float64")):
+            raise X3dError("snapshot_pack: the output type is float32 or float64")
+        nbytes = n * int(count[0]) * int(count[1]) * int(count[2]) * size
+        if out.numel() * out.element_size() < nbytes:
+            raise X3dError("snapshot_pack: the output buffer is smaller than the packed snapshot")
+        _lib.check(self.lib.x3d_snapshot_pack(self.h, ctypes.cast(tab, VP), n, self._dims(VERT), _lib.ints(*first),
+                                              _lib.ints(*stride), _lib.ints(*count), size, out.data_ptr()))
+        return nbytes
+
+    def snapshot_copy_async(self, host, dev, nbytes):
+        """the first nbytes of the device tensor dev -> the pinned host tensor host, on the copy stream, ordered behind
+        what is queued on the compute stream; returns the handle for snapshot_done / snapshot_wait.  The communication
+        stream serves if parallel.Comm has made one, else a stream the library owns."""
+        if not host.is_pinned():
+            raise X3dError("snapshot_copy_async: the host buffer must be pinned")
+        if min(host.numel() * host.element_size(), dev.numel() * dev.element_size()) < nbytes:
+            raise X3dError("snapshot_copy_async: a buffer is smaller than the copy")
+        cs = getattr(self.comm, "_cstream", None)
+        h = ctypes.c_int(-1)
+        _lib.check(self.lib.x3d_snapshot_copy_async(self.h, host.data_ptr(), dev.data_ptr(), int(nbytes),
+                                                    VP(cs.cuda_stream) if cs is not None else None, ctypes.byref(h)))
+        return h.value
+
+    def snapshot_done(self, handle):
+        """has the copy behind `handle` completed?  Never blocks."""
+        done = ctypes.c_int(0)
+        _lib.check(self.lib.x3d_snapshot_done(self.h, int(handle), ctypes.byref(done)))
+        return bool(done.value)
+
+    def snapshot_wait(self, handle):
+        """block until it has (counted by sync_count)"""
+        _lib.check(self.lib.x3d_snapshot_wait(self.h, int(handle)))
+
     # ------------------------------------------------------------ faces
     def field_set_face(self, f, c_start, c_end, face):
         if f.dir != DIR_X:

@@ -49,6 +49,7 @@ class BaseCase:
         self.solver = solver
         self.monitoring = Monitoring(solver)
         self.stats = None  # optional stats.Stats(solver, cfg): run() then samples and writes it (io_manager, base_case.f90:319-329)
+        self.snapshots = None  # optional snapshot.Snapshots(solver, cfg): run() then writes it (handle_io_step, :307-329)
         self.step_times = []
         self.initial_conditions()
 
@@ -144,12 +145,17 @@ class BaseCase:
         for f in deriv:  # (kept until the deferred updates that read them were done)
             al.release_block(f)
 
-    def step(self, it, more=False):
+    def step(self, it, more=False, want_pressure=False):
         """one time step.  more=True: another step follows at once and nothing looks at the fields in between, so
         the last sub-step's velocity correction may also wait for the next transeq_x kernel; whoever reads the
-        velocity next without going through step() must call solver.flush_grad() first (run() does)."""
-        ns = self.solver.time_integrator.nstage
+        velocity next without going through step() must call solver.flush_grad() first (run() does).
+        want_pressure: a snapshot of this step is due and solver.keep_pressure is set -- the fused driver then keeps
+        the pressure of the step's last sub-step (Solver.pressure_correction_fused)."""
+        s = self.solver
+        ns = s.time_integrator.nstage
         for i in range(ns):
+            if s.keep_pressure:  # (fused driver: only the last sub-step of a snapshot step keeps its pressure)
+                s.pressure_wanted = bool(want_pressure) and i == ns - 1
             self.substep(it, last=(i == ns - 1 and not more))
 
     def run(self, n_iters=None, verbose=False):
@@ -162,7 +168,11 @@ class BaseCase:
             output_due = s.n_output > 0 and it % s.n_output == 0
             # a statistics sample reads the velocity like an output step does
             sample_due = self.stats is not None and self.stats.cfg.sample_due(it)
-            self.step(it, more=(it < n_iters and not output_due and not sample_due))
+            # ... and so does a snapshot (snapshot_manager.f90:125-126)
+            snap = self.snapshots
+            snap_due = snap is not None and snap.cfg.due(it)
+            self.step(it, more=(it < n_iters and not output_due and not sample_due and not snap_due),
+                      want_pressure=snap_due and s.keep_pressure)
             s.current_iter = it
             if self.stats is not None:
                 self.stats.update(it)  # update_stats, base_case.f90:319
@@ -173,9 +183,14 @@ class BaseCase:
                           % (row[0], it, row[1], row[2], row[3]))
             if self.stats is not None:
                 self.stats.write(it)  # handle_io_step, base_case.f90:328
+            if snap is not None:
+                snap.write(it)  # packs and starts the copy; no host wait
+                snap.poll()     # files of the snapshots whose copies have landed
             s.backend.sync()
             self.step_times.append(time.perf_counter() - t0)
         s.flush_grad()
+        if self.snapshots is not None:
+            self.snapshots.finalise()
         return self.monitoring.rows
 
 

@@ -122,6 +122,7 @@ extern "C" int x3d_backend_destroy(x3d_backend *b)
     if (b->stats_part) hipFree(b->stats_part);
     if (b->bc_params) hipFree(b->bc_params);
     if (b->bc_part) hipFree(b->bc_part);
+    x3d_snapshot_destroy_c(b);
     hipEventDestroy(b->ev0); hipEventDestroy(b->ev1);
     delete static_cast<std::unordered_set<const void *> *>(b->lds_optin);
     x3d_lazy_destroy(b);

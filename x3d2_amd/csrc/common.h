@@ -172,8 +172,10 @@ struct x3d_backend {
     long stats_cap;      // ... its size in doubles
     real_t *bc_params;   // {out_vel, flow_rate_diff} of x3d_outflow_params (ibm.hip): read by x3d_cylinder_apply_bc on the device
     double *bc_part;     // ... its stage-1 partials, [X3D_BC_PARTS][3] = sum u[1], sum u[nx], max u[nx-1]
-    long n_sync;         // host waits for the stream inside the reductions and x3d_outflow_params_get (x3d_backend_counter 3)
+    long n_sync;         // host waits for the stream inside the reductions, x3d_outflow_params_get and x3d_snapshot_wait (x3d_backend_counter 3)
+    void *snap;          // snapshot copies in flight and the copy stream (snapshot.hip, struct x3d_snap), null until the first copy
 };
+void x3d_snapshot_destroy_c(x3d_backend *b);
 #define X3D_BC_PARTS 1024
 // the RK / AB stage of one variable as the epilogue of a tile kernel (xscan.hip, k_ytile_transeq<EPI> / k_ytile_transeq3<EPI>):
 // d = x[ipend] + component;  [store: x[ipend] = d;]  y = base + sum_k c[k] (k == ipend ? d : x[k])

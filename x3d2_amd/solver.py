@@ -141,6 +141,10 @@ class Solver:
             self.pressure_correction = self.pressure_correction_fused
         # solver%ibm (src/solver.f90, ibm_on): None = no immersed boundary, and BaseCase.substep is what it was
         self.ibm = None
+        # keep_pressure / pressure (src/solver.f90:60-61, 705-714): the last pressure stays in a block of its own for the
+        # snapshots (snapshot.Snapshots sets keep_pressure).  pressure_wanted: the fused driver keeps it only where the
+        # case asks (BaseCase.step: the last sub-step of a step whose snapshot is due), see pressure_correction_fused
+        self.keep_pressure, self.pressure, self.pressure_wanted = False, None, False
 
     # ---- src/solver.f90:291-389
     def transeq_default(self, rhs, variables):
@@ -394,6 +398,9 @@ class Solver:
         upd = self.time_integrator.pending_update
         walls, self.pending_walls = self.pending_walls or (None, None, None), None
         mean, self.mean_request, self._mean_ready = self.mean_request, None, None
+        # a snapshot wants this correction's pressure: on the z-first 000 and the row-interleaved 010 path it never exists
+        # as a field, so this one correction takes the plain z pair -> solve_poisson -> z pair and p is copied out
+        want_p = self.keep_pressure and self.pressure_wanted
         for out, fld, op, wall in ((t1, u, x.stagder_v2p, walls[0]), (t2, v, x.interpl_v2p, walls[1]),
                                    (t3, w, x.interpl_v2p, walls[2])):
             spec = upd.pop(fld.data.data_ptr(), None)
@@ -421,7 +428,7 @@ class Solver:
         nil = 0
         if self.cfg.poisson_solver_type == "FFT" and not b._decomposed(DIR_Y):
             nil = getattr(b.poisson_fft, "interleaved_rows", lambda: 0)()
-        if self._zfirst and b._decomposed(DIR_Y) and not b._decomposed(DIR_Z):
+        if self._zfirst and not want_p and b._decomposed(DIR_Y) and not b._decomposed(DIR_Z):
             # y slabs: z is whole on this rank, the z-first solve applies as on one rank (csrc/sfftz.hip)
             b.tds_jobs(DIR_Y, jy)
             if self._zfirst_solve(a1, a2, t2, t3):
@@ -431,7 +438,7 @@ class Solver:
             b.tds_jobs(DIR_Z, jz)
         elif b._decomposed(DIR_Y) or b._decomposed(DIR_Z):
             # (z slabs: the halo form of the interleaving pair, t2 as above)
-            nil = nil if nil and self._zpairs_interleave(nil, jz[0]) else 0
+            nil = nil if nil and not want_p and self._zpairs_interleave(nil, jz[0]) else 0
             if nil:
                 jz = [(0, t2, None, a1, a2, z.interpl_v2p, z.stagder_v2p)]
                 div = t2
@@ -442,11 +449,11 @@ class Solver:
             b.tds_apply(a2, t3, y.interpl_v2p, DIR_Y)
             # 000 solve at 512^3: z-first -- the z pairs on either side transform along z on their tiles, the divergence
             # and the pressure never exist as fields (csrc/zfirst.hip)
-            if self._zfirst and self._zfirst_solve(a1, a2, t2, t3):
+            if self._zfirst and not want_p and self._zfirst_solve(a1, a2, t2, t3):
                 b.tds_pair(1, a1, a2, t2, None, y.interpl_p2v, y.stagder_p2v, DIR_Y)   # p_sx, dpdy_sx
                 b.tds_apply(t1, t3, y.interpl_p2v, DIR_Y)                              # dpdz_sx
                 return self._finish_pressure_correction(u, v, w, (t1, t2, t3, a1, a2), defer_grad)
-            if nil and b.tds_pair_yperm(0, t2, None, a1, a2, z.interpl_v2p, z.stagder_v2p, nil):
+            if nil and not want_p and b.tds_pair_yperm(0, t2, None, a1, a2, z.interpl_v2p, z.stagder_v2p, nil):
                 div = t2  # (t2, t3 are free after the y stage) rows interleaved
                 self.n_interleaved += 1
             else:
@@ -460,6 +467,10 @@ class Solver:
             b.poisson_fft.solve_poisson(p, t2)  # t2 is free here: scratch of poisson_010
         else:
             p.fill(0.0)
+        if want_p:
+            if self.pressure is None:
+                self.pressure = al.get_block(DIR_X, CELL)  # (one layout for every DIR tag; never released)
+            b.veccopy(self.pressure, p)
         # gradient_c2v, :248-332, + velocity correction solver.f90:731-733
         if nil and b._decomposed(DIR_Z):
             jz = [(1, t1, t3, p, None, z.interpl_p2v, z.stagder_p2v)]    # as below, through the halo forms
@@ -625,12 +636,18 @@ class Solver:
         b, al = self.backend, self.backend.allocator
         div_u = al.get_block(DIR_Z)
         self.divergence_v2p(div_u, u, v, w)
-        p = al.get_block(DIR_Z)
+        if self.keep_pressure:  # :705-714: persist the pressure for snapshot output
+            if self.pressure is None:
+                self.pressure = al.get_block(DIR_Z, CELL)
+            p = self.pressure
+        else:
+            p = al.get_block(DIR_Z)
         self.poisson(p, div_u)
         al.release_block(div_u)
         dpdx, dpdy, dpdz = (al.get_block(DIR_X) for _ in range(3))
         self.gradient_p2v(dpdx, dpdy, dpdz, p)
-        al.release_block(p)
+        if not self.keep_pressure:
+            al.release_block(p)
         b.vecadd(-1.0, dpdx, 1.0, u)
         b.vecadd(-1.0, dpdy, 1.0, v)
         b.vecadd(-1.0, dpdz, 1.0, w)
