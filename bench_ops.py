@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -28,6 +28,11 @@ touched source lines plus output bytes (a 128-byte line counts whole when one of
 6.2 TB/s copy ceiling; (b) host-visible time of Snapshots.write from call to return against the composed path in the
 same process (six get_field_data, two compute_*, numpy striding and astype); (c) a 20-step TGV run at snapshot_freq = 5
 against the same run without snapshots: added wall time per snapshot.
+
+Family "checkpoint" (--snap-n^3 = 512^3, median of --stat-iters; not part of "all"): (a) the pack launch with its checksums
+for 3 and for 12 blocks against the 6.2 TB/s copy ceiling; (b) Checkpoints.write from call to return against get_field_data
+of the same 12 blocks; (c) a 20-step TGV run at checkpoint_freq = 5 against the same run without checkpoints, and the time
+poll() spent writing files on the host thread.
 """
 import argparse
 import json
@@ -332,12 +337,104 @@ def bench_snapshot(args):
                       "added_ms_per_snapshot": (res[True] - res[False]) / 4.0}), flush=True)
 
 
+def bench_checkpoint(args):
+    """one JSON line per measurement of the "checkpoint" family"""
+    import ctypes
+    import tempfile
+
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.checkpoint import CheckpointConfig, Checkpoints
+    from x3d2_amd.common import DIR_X, VERT
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    tmp = tempfile.mkdtemp(prefix="x3d_ckpt_")
+    case = make_tgv(n, fused=True, time_intg="AB4")
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    case.step(1)
+    s.flush_grad()
+    dims = tuple(int(v) for v in s.mesh.get_dims(VERT))
+    npts = int(np.prod(dims))
+    state = [s.u, s.v, s.w] + [f for row in s.time_integrator.olds for f in row]  # 12 blocks
+
+    # (a) the pack launch alone, 3 and 12 blocks
+    for nblock in (3, 12):
+        _, _, total = b.checkpoint_layout(nblock, npts)
+        buf = torch.empty(total, dtype=torch.uint8, device=b.device)
+        ms, times = ctypes.c_float(), []
+        for i in range(args.stat_warmup + args.stat_iters):
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            b.checkpoint_pack(state[:nblock], dims, buf)
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times.append(ms.value)
+        t = float(np.median(times))
+        moved = 2 * nblock * npts * rb  # every interior element read once and written once
+        print(json.dumps({"family": "checkpoint", "op": "pack with checksums", "n": n, "blocks": nblock, "real_bytes": rb,
+                          "ms_median": t, "ms_min": float(min(times)), "launches": len(times), "bytes": moved,
+                          "GBs": moved / t / 1e6, "ceiling": moved / t / 1e6 / 6200.0, "row_pitch": b.padded_dims[0]}),
+              flush=True)
+        del buf
+    torch.cuda.empty_cache()
+
+    # (b) host-visible cost of Checkpoints.write against the only route there was: get_field_data of the same blocks
+    ck = Checkpoints(s, CheckpointConfig(checkpoint_freq=1, checkpoint_prefix=os.path.join(tmp, "b")), case)
+    for name, fn, after in (("Checkpoints.write, call to return", lambda it: ck.write(it), lambda: ck.pending and b.snapshot_wait(ck.pending[1])),
+                            ("composed: 12 get_field_data", lambda it: [b.get_field_data(f, VERT) for f in state], None)):
+        walls, s0 = [], b.sync_count()
+        for i in range(2 + 5):
+            b.sync()
+            t0 = time.perf_counter()
+            fn(i + 1)
+            w = (time.perf_counter() - t0) * 1e3
+            if after is not None:
+                after()  # (outside the timed region: the copy has landed; no file is written here)
+                ck.pending = None
+            if i >= 2:
+                walls.append(w)
+        print(json.dumps({"family": "checkpoint", "op": name, "n": n, "blocks": 12, "wall_ms_median": float(np.median(walls)),
+                          "wall_ms_min": float(min(walls)), "calls": len(walls), "stream_syncs": b.sync_count() - s0}), flush=True)
+    del ck, case, s, b, al, state
+    torch.cuda.empty_cache()
+
+    # (c) a 20-step run with and without checkpoints; poll() writes the file on the host thread (np.savez)
+    res, in_poll = {}, 0.0
+    for with_ckpt in (False, True):
+        case = make_tgv(n, fused=True)
+        if with_ckpt:
+            ck = Checkpoints(case.solver, CheckpointConfig(checkpoint_freq=5, checkpoint_prefix=os.path.join(tmp, "c"),
+                                                           keep_checkpoint=False), case)
+            inner = ck._write_file
+
+            def timed_write():
+                nonlocal in_poll
+                t1 = time.perf_counter()
+                out = inner()
+                in_poll += (time.perf_counter() - t1) * 1e3
+                return out
+
+            ck._write_file = timed_write
+            case.checkpoints = ck
+        case.run(n_iters=3)
+        case.solver.backend.sync()
+        in_poll = 0.0
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        case.solver.backend.sync()
+        res[with_ckpt] = (time.perf_counter() - t0) * 1e3
+        del case
+        torch.cuda.empty_cache()
+    print(json.dumps({"family": "checkpoint", "op": "TGV, fused, RK3: 20 steps, checkpoint_freq 5", "n": n,
+                      "wall_ms_without": res[False], "wall_ms_with": res[True], "checkpoints": 4,
+                      "added_ms_per_checkpoint": (res[True] - res[False]) / 4.0, "ms_in_file_writes": in_poll}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot"))
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -348,7 +445,9 @@ def main():
         bench_ibm(args)
     if args.family == "snapshot":
         bench_snapshot(args)
-    if args.family in ("stats", "ibm", "snapshot"):
+    if args.family == "checkpoint":
+        bench_checkpoint(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint"):
         return
     import torch
     from x3d2_amd import Mesh

@@ -794,6 +794,27 @@ int x3d_snapshot_done(x3d_backend *b, int handle, int *done);
 /* blocks the host until it has; counted by x3d_backend_counter(b, 3) */
 int x3d_snapshot_wait(x3d_backend *b, int handle);
 
+/* ---- checkpoints (csrc/checkpoint.hip): the device side of checkpoint_manager_t (src/io/checkpoint_manager.f90).  The
+ * reference pulls every variable of the state to the host with one blocking copy each; here one launch packs the whole state
+ * and forms its checksums, x3d_snapshot_copy_async / _done / _wait move the packed buffer, and one launch unpacks it. */
+#define X3D_CKPT_MAXBLOCK 64 /* blocks per launch: their addresses travel as kernel arguments */
+/* out[k][z][y][x] (dense, x fastest, in the real kind) = the dims interior of blocks[k], its bits unchanged, the row padding
+ * dropped; blocks: a HOST array of nblock <= X3D_CKPT_MAXBLOCK device blocks (more: an error, nothing is launched).  The same
+ * launch fills table[k][0..2] on the device (zeroed behind the launch's predecessors on the stream, not by the host), with i
+ * the dense index of an element within its block and bits() its bit pattern (zero-extended to 64 bits on 4-byte reals):
+ *   table[k][0] = sum bits(e_i)  mod 2^64,   table[k][1] = sum bits(e_i) (2 i + 1)  mod 2^64,
+ *   table[k][2] = the number of elements that are NaN or +-Inf.
+ * If a copy of `out` started by x3d_snapshot_copy_async is still in flight the launch waits for it on the device.  No host
+ * synchronisation. */
+int x3d_checkpoint_pack(x3d_backend *b, const x3d_real *const *blocks, int nblock, const int dims[3], void *out,
+                        unsigned long long *table);
+/* the same table from a dense buffer alone: nblock blocks of n_per_block elements each */
+int x3d_checkpoint_sums(x3d_backend *b, const void *dense, int nblock, long n_per_block, unsigned long long *table);
+/* the inverse of the pack: the dims interior of blocks[k] <- dense[k], every other element of the block (block_elems =
+ * x3d_block_elems: row padding, rows and planes beyond dims) <- +0.0, as the reference fills with 0 before set_field_data */
+int x3d_checkpoint_unpack(x3d_backend *b, x3d_real *const *blocks, int nblock, const int dims[3], long block_elems,
+                          const void *dense);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -246,6 +246,9 @@ PROTOTYPES = {
     "x3d_snapshot_copy_async": (I, [VP, VP, VP, ctypes.c_long, VP, c_int_p]),
     "x3d_snapshot_done": (I, [VP, I, c_int_p]),
     "x3d_snapshot_wait": (I, [VP, I]),
+    "x3d_checkpoint_pack": (I, [VP, ctypes.POINTER(VP), I, c_int_p, VP, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "x3d_checkpoint_sums": (I, [VP, VP, I, ctypes.c_long, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "x3d_checkpoint_unpack": (I, [VP, ctypes.POINTER(VP), I, c_int_p, ctypes.c_long, VP]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),

@@ -1122,6 +1122,67 @@ class HipBackend:
         """block until it has (counted by sync_count)"""
         _lib.check(self.lib.x3d_snapshot_wait(self.h, int(handle)))
 
+    # ------------------------------------------------------------ checkpoints (csrc/checkpoint.hip)
+    CKPT_MAXBLOCK = 64  # X3D_CKPT_MAXBLOCK of include/x3d2_hip.h
+
+    @staticmethod
+    def checkpoint_layout(nblock, n_per_block):
+        """(bytes of the packed data, offset of the checksum table, bytes of buffer) for nblock blocks of n_per_block
+        elements: the table [nblock][3] of 8-byte integers rides behind the data, on a 16-byte boundary"""
+        data = int(nblock) * int(n_per_block) * np.dtype(_lib.NP_REAL).itemsize
+        off = (data + 15) // 16 * 16
+        return data, off, off + int(nblock) * 24
+
+    def checkpoint_buffers(self, nbytes):
+        """(device staging buffer, pinned host buffer) of nbytes each"""
+        return (torch.empty(int(nbytes), dtype=torch.uint8, device=self.device),
+                torch.empty(int(nbytes), dtype=torch.uint8, pin_memory=True))
+
+    def _block_table(self, fields, who):
+        n = len(fields)
+        if not 1 <= n <= self.CKPT_MAXBLOCK:
+            raise X3dError(f"{who}: 1 .. {self.CKPT_MAXBLOCK} blocks per launch (got {n})")
+        return (VP * n)(*[f.ptr for f in fields])
+
+    def checkpoint_pack(self, fields, dims, buf):
+        """one launch for a whole state: buf (a device byte tensor laid out by checkpoint_layout) <- the dims interior
+        of every field, densely as [block][z][y][x], and behind it the table of (s1, s2, nonfinite) per block.
+        Returns the bytes to copy.  No host synchronisation."""
+        tab = self._block_table(fields, "checkpoint_pack")
+        n = int(dims[0]) * int(dims[1]) * int(dims[2])
+        _, off, total = self.checkpoint_layout(len(fields), n)
+        if buf.numel() * buf.element_size() < total:
+            raise X3dError("checkpoint_pack: the buffer is smaller than the packed state")
+        _lib.check(self.lib.x3d_checkpoint_pack(self.h, tab, len(fields), _lib.ints(*dims), buf.data_ptr(),
+                                                ctypes.cast(buf.data_ptr() + off, ctypes.POINTER(ctypes.c_ulonglong))))
+        return total
+
+    def checkpoint_sums(self, buf, nblock, n_per_block):
+        """the table of a dense state already in buf, written behind it like checkpoint_pack does; no host wait"""
+        _, off, total = self.checkpoint_layout(nblock, n_per_block)
+        if buf.numel() * buf.element_size() < total:
+            raise X3dError("checkpoint_sums: the buffer is smaller than the packed state")
+        _lib.check(self.lib.x3d_checkpoint_sums(self.h, buf.data_ptr(), int(nblock), int(n_per_block),
+                                                ctypes.cast(buf.data_ptr() + off, ctypes.POINTER(ctypes.c_ulonglong))))
+
+    def checkpoint_table(self, buf, nblock, n_per_block):
+        """the table behind the data of a device buffer, on the host as uint64 [nblock, 3] (one host wait)"""
+        _, off, total = self.checkpoint_layout(nblock, n_per_block)
+        return buf[off:total].cpu().numpy().view(np.uint64).reshape(int(nblock), 3)
+
+    def checkpoint_upload(self, buf, host, nbytes):
+        """the first nbytes of the pinned host tensor -> the device buffer, ordered on the compute stream"""
+        buf[:int(nbytes)].copy_(host[:int(nbytes)], non_blocking=True)
+
+    def checkpoint_unpack(self, fields, dims, buf):
+        """the inverse of checkpoint_pack in one launch: interiors from buf, every other element of the blocks 0"""
+        tab = self._block_table(fields, "checkpoint_unpack")
+        n = int(dims[0]) * int(dims[1]) * int(dims[2])
+        data, _, _ = self.checkpoint_layout(len(fields), n)
+        if buf.numel() * buf.element_size() < data:
+            raise X3dError("checkpoint_unpack: the buffer is smaller than the packed state")
+        _lib.check(self.lib.x3d_checkpoint_unpack(self.h, tab, len(fields), _lib.ints(*dims), self.nblock, buf.data_ptr()))
+
     # ------------------------------------------------------------ faces
     def field_set_face(self, f, c_start, c_end, face):
         if f.dir != DIR_X:

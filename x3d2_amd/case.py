@@ -50,6 +50,10 @@ class BaseCase:
         self.monitoring = Monitoring(solver)
         self.stats = None  # optional stats.Stats(solver, cfg): run() then samples and writes it (io_manager, base_case.f90:319-329)
         self.snapshots = None  # optional snapshot.Snapshots(solver, cfg): run() then writes it (handle_io_step, :307-329)
+        # optional checkpoint.Checkpoints(solver, cfg, case): run() then writes it (handle_io_step); restarted is set by
+        # checkpoint.restore (io_mgr%is_restart, :212)
+        self.checkpoints = None
+        self.restarted = False
         self.step_times = []
         self.initial_conditions()
 
@@ -89,6 +93,14 @@ class BaseCase:
 
     def postprocess(self, it, t):
         return self.monitoring.write_step(t, self.solver.u, self.solver.v, self.solver.w)
+
+    def checkpoint_state(self):
+        """checkpoint_state_t (src/io/checkpoint_state.f90): what a restarted run needs of the case beyond the solver's
+        fields, as a dict of scalars; written under `case_<key>` by checkpoint.Checkpoints"""
+        return {}
+
+    def load_checkpoint_state(self, state):
+        pass
 
     def substep(self, it, last=True):
         """body of the sub_iter loop, base_case.f90:261-289"""
@@ -161,6 +173,8 @@ class BaseCase:
     def run(self, n_iters=None, verbose=False):
         s = self.solver
         n_iters = s.n_iters if n_iters is None else n_iters
+        if self.restarted and n_iters <= s.current_iter:  # base_case.f90:218-221
+            raise X3dError("Restart requires n_iters greater than the restart iteration.")
         self.postprocess(s.current_iter, s.current_iter * s.dt)
         start = s.current_iter + 1
         for it in range(start, n_iters + 1):
@@ -171,6 +185,10 @@ class BaseCase:
             # ... and so does a snapshot (snapshot_manager.f90:125-126)
             snap = self.snapshots
             snap_due = snap is not None and snap.cfg.due(it)
+            # ... and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step)
+            ckpt = self.checkpoints
+            if ckpt is not None and ckpt.cfg.due(it):
+                output_due = True
             self.step(it, more=(it < n_iters and not output_due and not sample_due and not snap_due),
                       want_pressure=snap_due and s.keep_pressure)
             s.current_iter = it
@@ -186,11 +204,16 @@ class BaseCase:
             if snap is not None:
                 snap.write(it)  # packs and starts the copy; no host wait
                 snap.poll()     # files of the snapshots whose copies have landed
+            if ckpt is not None:
+                ckpt.write(it)  # one pack launch, one asynchronous copy; no host wait
+                ckpt.poll()     # the file of a checkpoint whose copy has landed
             s.backend.sync()
             self.step_times.append(time.perf_counter() - t0)
         s.flush_grad()
         if self.snapshots is not None:
             self.snapshots.finalise()
+        if self.checkpoints is not None:
+            self.checkpoints.finalise()
         return self.monitoring.rows
 
 
@@ -280,6 +303,12 @@ class ChannelCase(BaseCase):
             for c, (f, n) in enumerate(zip(self.bc_start_y, noise)):
                 b.wall_noise(f, n, self.noise_seed, 3 * self.noise_draws + c)
             self.noise_draws += 1
+
+    def checkpoint_state(self):
+        return {"noise_seed": np.uint64(self.noise_seed), "noise_draws": np.int64(self.noise_draws)}
+
+    def load_checkpoint_state(self, state):
+        self.noise_seed, self.noise_draws = int(state["noise_seed"]), int(state["noise_draws"])
 
     def substep(self, it, last=True):
         c, s = self.channel_cfg, self.solver
@@ -393,6 +422,15 @@ class CylinderCase(BaseCase):
             for c, (f, base, n) in enumerate(zip(self.bc_start_x, (1.0, 0.0, 0.0), noise)):
                 b.inlet_noise(f, base, n * um, self.noise_seed, 3 * self.noise_draws + c)
             self.noise_draws += 1
+
+    def checkpoint_state(self):
+        # (out_vel / flow_rate_diff: the row postprocess writes before the restarted run's first define_BC)
+        return {"noise_seed": np.uint64(self.noise_seed), "noise_draws": np.int64(self.noise_draws),
+                "out_vel": np.float64(self.out_vel), "flow_rate_diff": np.float64(self.flow_rate_diff)}
+
+    def load_checkpoint_state(self, state):
+        self.noise_seed, self.noise_draws = int(state["noise_seed"]), int(state["noise_draws"])
+        self.out_vel, self.flow_rate_diff = float(state["out_vel"]), float(state["flow_rate_diff"])
 
     def apply_BC(self, u, v, w):  # :226-243
         fu, fv, fw = self.bc_start_x

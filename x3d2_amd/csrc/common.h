@@ -176,6 +176,9 @@ struct x3d_backend {
     void *snap;          // snapshot copies in flight and the copy stream (snapshot.hip, struct x3d_snap), null until the first copy
 };
 void x3d_snapshot_destroy_c(x3d_backend *b);
+// the backend's stream waits (on the device) for a copy out of the packed buffer `dev` that x3d_snapshot_copy_async started
+// and that may still be in flight; nothing to do if there is none (snapshot.hip; checkpoint.hip packs into such buffers too)
+int x3d_snapshot_wait_for_copy_c(x3d_backend *b, const void *dev);
 #define X3D_BC_PARTS 1024
 // the RK / AB stage of one variable as the epilogue of a tile kernel (xscan.hip, k_ytile_transeq<EPI> / k_ytile_transeq3<EPI>):
 // d = x[ipend] + component;  [store: x[ipend] = d;]  y = base + sum_k c[k] (k == ipend ? d : x[k])

@@ -125,6 +125,13 @@ void x3d_snapshot_destroy_c(x3d_backend *b)
     b->snap = nullptr;
 }
 
+int x3d_snapshot_wait_for_copy_c(x3d_backend *b, const void *dev)
+{
+    if (SnapSlot *s = snap_find(b, dev))
+        if (s->copied) X3D_HIP(hipStreamWaitEvent(b->stream, s->ev_done, 0));
+    return 0;
+}
+
 extern "C" int x3d_snapshot_pack(x3d_backend *b, const x3d_snapshot_var *vars, int nvar, const int dims[3],
                                  const int first[3], const int stride[3], const int count[3], int out_bytes, void *out)
 {
@@ -158,8 +165,7 @@ extern "C" int x3d_snapshot_pack(x3d_backend *b, const x3d_snapshot_var *vars, i
         for (int m = 0; m < (T.v[v].kind == X3D_SNAP_COPY ? 1 : 9); m++) X3D_LAZY_IN(b, T.v[v].src[m]);
     X3D_LAZY_EAGER(b);
     // a copy of this buffer's previous contents may still be in flight: the pack waits for it on the device
-    if (SnapSlot *s = snap_find(b, out))
-        if (s->copied) X3D_HIP(hipStreamWaitEvent(b->stream, s->ev_done, 0));
+    if (int rc = x3d_snapshot_wait_for_copy_c(b, out)) return rc;
     SnapGeom G;
     for (int d = 0; d < 3; d++) { G.first[d] = first[d]; G.stride[d] = stride[d]; G.count[d] = count[d]; }
     G.nxp = b->nxp;
