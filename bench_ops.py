@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -33,6 +33,13 @@ Family "checkpoint" (--snap-n^3 = 512^3, median of --stat-iters; not part of "al
 for 3 and for 12 blocks against the 6.2 TB/s copy ceiling; (b) Checkpoints.write from call to return against get_field_data
 of the same 12 blocks; (c) a 20-step TGV run at checkpoint_freq = 5 against the same run without checkpoints, and the time
 poll() spent writing files on the host thread.
+
+Family "spectra" (--snap-n^3 = 512^3, HIP-event time, median of --stat-iters; not part of "all"): (a) the shell-binning
+launches alone (x3d_spectra_reduce) against the bytes they must read, nz ny nxs complex numbers, and the 6.2 TB/s copy
+ceiling, next to x3d_scalar_product on a field of the same run; (b) a whole three-field sample, three forward transforms
+plus three reductions plus the running-mean update; (c) the composed path in the same process, get_spectral plus numpy
+binning for three fields (wall clock: it waits for the host); (d) the plane reduction alone and a three-field plane sample
+at 1024 x 257 x 512.  `step_share` = fraction of the 40 ms of a 512^3 TGV step (README).
 """
 import argparse
 import json
@@ -429,12 +436,103 @@ def bench_checkpoint(args):
                       "added_ms_per_checkpoint": (res[True] - res[False]) / 4.0, "ms_in_file_writes": in_poll}), flush=True)
 
 
+def bench_spectra(args):
+    """one JSON line per case of the "spectra" family"""
+    import ctypes
+
+    import torch
+    from x3d2_amd import _lib, make_channel, make_tgv
+    from x3d2_amd.spectra import Spectra, SpectraConfig
+    rb = 4 if _lib.SINGLE else 8
+
+    def timed(b, fn):
+        ms, times = ctypes.c_float(), []
+        for i in range(args.stat_warmup + args.stat_iters):
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            fn()
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times.append(ms.value)
+        return float(np.median(times)), float(min(times)), len(times)
+
+    def row(op, dims, t, tmin, n, nbytes=None, **more):
+        out = {"op": op, "dims": list(dims), "real_bytes": rb, "ms_median": t, "ms_min": tmin, "launches": n,
+               "step_share": t / 40.0}
+        if nbytes is not None:
+            out.update(bytes=nbytes, GBs=nbytes / t / 1e6, ceiling=nbytes / t / 1e6 / 6200.0)
+        out.update(more)
+        print(json.dumps(out), flush=True)
+
+    n = args.snap_n
+    case = make_tgv(n, fused=True)
+    s = case.solver
+    b = s.backend
+    sp = Spectra(s, SpectraConfig(mode="shell", initspec=1))
+    pf = b.poisson_fft
+    nxs = (n // 2 + 1 + 7) // 8 * 8
+    spec_bytes = n * n * nxs * 2 * rb
+    sp.sample()
+    t, tmin, k = timed(b, lambda: _lib.check(b.lib.x3d_spectra_reduce(sp.h, pf.h, 0)))
+    row("spectra: shell binning alone (one field)", (n, n, n), t, tmin, k, spec_bytes, nbins=sp.layout.nbins,
+        workgroups=sp.groups)
+    t, tmin, k = timed(b, lambda: b.scalar_product(s.u, s.v))
+    row("scalar_product (k_reduce) on the same box", (n, n, n), t, tmin, k, 2 * rb * n ** 3)
+    t, tmin, k = timed(b, sample_of(sp))
+    row("spectra: three-field shell sample (3 transforms + 3 binnings + mean)", (n, n, n), t, tmin, k)
+
+    # the composed path: the spectrum to the host, binned there (what the device reduction replaces)
+    m = np.arange(n)
+    k1 = np.where(m <= n // 2, m, m - n).astype(np.float64) ** 2
+    wx = np.full(n // 2 + 1, 2.0)
+    wx[0] = 1.0
+    if n % 2 == 0:
+        wx[n // 2] = 1.0
+    bins = np.floor(np.sqrt((k1[None, None, :n // 2 + 1] + k1[None, :, None]) + k1[:, None, None]) / sp.layout.dk
+                    + 0.5).astype(np.int64).reshape(-1)
+    times = []
+    for _ in range(2):  # (seconds each: the host bins 3 x 67 million modes)
+        b.sync()
+        t0 = time.perf_counter()
+        for f in (s.u, s.v, s.w):
+            pf.fft_forward(f)
+            c = pf.get_spectral()
+            e = (0.5 * wx)[None, None, :] * (c.real * c.real + c.imag * c.imag) / float(n) ** 6
+            np.bincount(bins, weights=e.reshape(-1), minlength=sp.layout.nbins)
+        times.append((time.perf_counter() - t0) * 1e3)
+    row("spectra: composed, get_spectral + numpy binning, three fields (wall clock)", (n, n, n), float(np.median(times)),
+        float(min(times)), len(times))
+    del case, s, sp, pf, b, bins
+    torch.cuda.empty_cache()
+    # plane mode at the channel's production size
+    dims = (1024, 257, 512)
+    case = make_channel(dims, L=(8.0, 2.0, 4.0), fused=True)
+    s = case.solver
+    b = s.backend
+    sp = Spectra(s, SpectraConfig(mode="plane", initspec=1))
+    sp.sample()
+    pnxs = (dims[0] // 2 + 1 + 7) // 8 * 8
+    t, tmin, k = timed(b, lambda: _lib.check(b.lib.x3d_spectra_reduce(sp.h, None, 0)))
+    row("spectra: plane reduction alone (one field)", dims, t, tmin, k, dims[2] * dims[1] * pnxs * 2 * rb, workgroups=sp.groups)
+    t, tmin, k = timed(b, sample_of(sp))
+    row("spectra: three-field plane sample (3 2-D transforms + 3 reductions + mean)", dims, t, tmin, k)
+
+
+def sample_of(sp):
+    count = [sp.sample_count]
+
+    def sample():
+        count[0] += 1
+        sp.update(count[0])
+
+    return sample
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint"))
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -447,7 +545,9 @@ def main():
         bench_snapshot(args)
     if args.family == "checkpoint":
         bench_checkpoint(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint"):
+    if args.family == "spectra":
+        bench_spectra(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra"):
         return
     import torch
     from x3d2_amd import Mesh

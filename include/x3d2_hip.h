@@ -815,6 +815,47 @@ int x3d_checkpoint_sums(x3d_backend *b, const void *dense, int nblock, long n_pe
 int x3d_checkpoint_unpack(x3d_backend *b, x3d_real *const *blocks, int nblock, const int dims[3], long block_elems,
                           const void *dense);
 
+/* ---- energy spectra on the device (csrc/spectrum.hip).  Not in the reference: this project's own addition, like the
+ * profile mode of the statistics.  One rank only.  Two modes:
+ *   X3D_SPECTRA_SHELL  all three directions periodic.  With C the plain DFT of a field (what x3d_poisson_fft_forward leaves
+ *       in the solver's workspace), N = nx ny nz, k = 2 pi m / L with m the signed mode number and w(kx) the Hermitian weight
+ *       of the half spectrum (1 for kx = 0 and for the Nyquist mode of an even nx, 2 otherwise):
+ *         E[b] = sum over the modes with  b = floor(sqrt((kx^2 + ky^2) + kz^2) / dk + 0.5)  of  1/2 w(kx) |C|^2 / N^2
+ *       -- the bin expression in FP64 and in exactly this order of operations.  dk <= 0: dk = max_i (2 pi / L_i).
+ *       nbins = floor(sqrt(sum_i (pi n_i / L_i)^2) / dk + 0.5) + 1; more than 4096 bins: an error.  sum_b E[b] = 1/2 <f^2>.
+ *   X3D_SPECTRA_PLANE  x and z periodic, y anything.  A 2-D real-to-complex plan over (z, x), batched over the vertex y rows,
+ *       and a workspace [nz][ny][nxs] complex of this object (about 0.56 GB at 1024 x 257 x 512 in FP64).  Per slot and y row:
+ *         E_x[y][kx] = sum over all kz of w(kx) 1/2 |C|^2 / (nx nz)^2,   kx = 0 .. nx/2   (one-sided)
+ *         E_z[y][kz] = the same summed over kx, kz = 0 .. nz/2, the modes kz and nz - kz added in that order
+ *       A slot holds E_x[ny][nx/2+1] followed by E_z[ny][nz/2+1].  sum_kx E_x[y] = sum_kz E_z[y] = 1/2 <f^2> of the plane.
+ * Every array of bins -- instantaneous, running mean, partial sums -- is double in BOTH flavours of the library.  The
+ * reductions are deterministic: no floating-point atomics, fixed-order partial sums, a fixed-order second stage on the device;
+ * two samples of the same field give the same bits.  A failed call leaves every array as it was. */
+typedef struct x3d_spectra x3d_spectra;
+enum { X3D_SPECTRA_SHELL = 0, X3D_SPECTRA_PLANE = 1 };
+/* dims: the vertex dims, which must be the backend's own (anything else is a decomposed mesh: an error); periodic[d] != 0:
+ * direction d is periodic; L: the box lengths; nslots: how many fields are sampled (1 .. 64).  The tables kx^2[nx/2+1],
+ * ky^2[ny], kz^2[nz] = (2 pi m / L)^2 are computed on the host in FP64.  All arrays start at zero. */
+int x3d_spectra_create(x3d_backend *b, x3d_spectra **out, int mode, const int dims[3], const int periodic[3],
+                       const double L[3], double dk, int nslots);
+int x3d_spectra_destroy(x3d_spectra *s);
+/* out = {mode, nslots, nbins, values per slot, nx/2+1, nz/2+1, ny, workgroups of the reduction launch}; dk (may be NULL) */
+int x3d_spectra_sizes(const x3d_spectra *s, long out[8], double *dk);
+/* the instantaneous spectrum of `field` (a VERT block) -> slot.  Shell mode: p = the backend's FFT Poisson object (its cell
+ * dims must be the vertex dims, else an error), x3d_poisson_fft_forward(p, field) and one reduction launch + its second stage;
+ * the solver's spectral workspace is overwritten, the field is not.  Plane mode: p is ignored (NULL), the object's own plan.
+ * A queue of the deferred-execution layer is flushed first.  No host synchronisation. */
+int x3d_spectra_sample(x3d_spectra *s, x3d_poisson *p, const x3d_real *field, int slot);
+/* the reduction launches alone, on whatever the spectral workspace holds (shell: p's; plane: the object's own): bench_ops.py */
+int x3d_spectra_reduce(x3d_spectra *s, x3d_poisson *p, int slot);
+/* one launch over all slots: mean += (inst - mean) / count -- accumulate_mean of the statistics; count = samples so far >= 1 */
+int x3d_spectra_accumulate(x3d_spectra *s, long count);
+/* host[nslots][values per slot] <- which = 0: the instantaneous arrays, 1: the running means.  The only call that waits for
+ * the stream. */
+int x3d_spectra_read(x3d_spectra *s, int which, double *host);
+/* the running means <- host[nslots][values per slot] (restart) */
+int x3d_spectra_load(x3d_spectra *s, const double *host_mean);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -249,6 +249,14 @@ PROTOTYPES = {
     "x3d_checkpoint_pack": (I, [VP, ctypes.POINTER(VP), I, c_int_p, VP, ctypes.POINTER(ctypes.c_ulonglong)]),
     "x3d_checkpoint_sums": (I, [VP, VP, I, ctypes.c_long, ctypes.POINTER(ctypes.c_ulonglong)]),
     "x3d_checkpoint_unpack": (I, [VP, ctypes.POINTER(VP), I, c_int_p, ctypes.c_long, VP]),
+    "x3d_spectra_create": (I, [VP, ctypes.POINTER(VP), I, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, I]),
+    "x3d_spectra_destroy": (I, [VP]),
+    "x3d_spectra_sizes": (I, [VP, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double)]),
+    "x3d_spectra_sample": (I, [VP, VP, VP, I]),
+    "x3d_spectra_reduce": (I, [VP, VP, I]),
+    "x3d_spectra_accumulate": (I, [VP, ctypes.c_long]),
+    "x3d_spectra_read": (I, [VP, I, ctypes.POINTER(ctypes.c_double)]),
+    "x3d_spectra_load": (I, [VP, ctypes.POINTER(ctypes.c_double)]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),

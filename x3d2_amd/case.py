@@ -49,6 +49,7 @@ class BaseCase:
         self.solver = solver
         self.monitoring = Monitoring(solver)
         self.stats = None  # optional stats.Stats(solver, cfg): run() then samples and writes it (io_manager, base_case.f90:319-329)
+        self.spectra = None  # optional spectra.Spectra(solver, cfg): run() then samples and writes it (not in the reference)
         self.snapshots = None  # optional snapshot.Snapshots(solver, cfg): run() then writes it (handle_io_step, :307-329)
         # optional checkpoint.Checkpoints(solver, cfg, case): run() then writes it (handle_io_step); restarted is set by
         # checkpoint.restore (io_mgr%is_restart, :212)
@@ -182,6 +183,9 @@ class BaseCase:
             output_due = s.n_output > 0 and it % s.n_output == 0
             # a statistics sample reads the velocity like an output step does
             sample_due = self.stats is not None and self.stats.cfg.sample_due(it)
+            # ... a spectra sample too
+            if self.spectra is not None and self.spectra.cfg.sample_due(it):
+                sample_due = True
             # ... and so does a snapshot (snapshot_manager.f90:125-126)
             snap = self.snapshots
             snap_due = snap is not None and snap.cfg.due(it)
@@ -194,6 +198,8 @@ class BaseCase:
             s.current_iter = it
             if self.stats is not None:
                 self.stats.update(it)  # update_stats, base_case.f90:319
+            if self.spectra is not None:
+                self.spectra.update(it)  # the transforms and the reductions; no host wait
             if s.n_output > 0 and it % s.n_output == 0:
                 row = self.postprocess(it, it * s.dt)
                 if verbose and s.mesh.is_root():
@@ -201,6 +207,8 @@ class BaseCase:
                           % (row[0], it, row[1], row[2], row[3]))
             if self.stats is not None:
                 self.stats.write(it)  # handle_io_step, base_case.f90:328
+            if self.spectra is not None:
+                self.spectra.write(it)
             if snap is not None:
                 snap.write(it)  # packs and starts the copy; no host wait
                 snap.poll()     # files of the snapshots whose copies have landed

@@ -11,7 +11,8 @@ for it.  One device and one host buffer: a checkpoint that arrives before the pr
 
 The state, in this order: u, v, w; phi_<n> per species; for Adams-Bashforth of order > 1 `<name>_rhs_old<j>` for every
 variable in the integrator's list order (after its rotations); with active 3-D statistics their accumulators under
-Stats.state_dict's names (the profile mode's few KB go through state_dict on the host).
+Stats.state_dict's names (the profile mode's few KB go through state_dict on the host, and so do the running means of
+case.spectra under Spectra.state_dict's `spectra_*` names).
 
 Scalars.  The reference's: timestep, time, dt, data_loc, ti_is_ab, ti_order, ti_istep, ti_nstep, stats_sample_count.
 Added here, because a resumed run must give the bits of the uninterrupted one:
@@ -108,6 +109,10 @@ class Checkpoints:
     def stats(self):
         return getattr(self.case, "stats", None) if self.case is not None else None
 
+    @property
+    def spectra(self):
+        return getattr(self.case, "spectra", None) if self.case is not None else None
+
     def _file_name(self, it, tag=""):
         m = self.solver.mesh
         return file_name(self.cfg.checkpoint_prefix, it, m.nproc, m.nrank, tag)
@@ -132,6 +137,9 @@ class Checkpoints:
             if st.cfg.profile_dir is not None:  # the profiles: a few KB, through the host
                 out.update(st.state_dict())
             out["stats_profile_dir"] = np.int64(st.cfg.profile_dir or 0)
+        sp = self.spectra
+        if sp is not None and sp.cfg.active:  # the running means of the spectra: a few KB to a few MB, through the host
+            out.update(sp.state_dict())
         if self.case is not None:
             for k, v in self.case.checkpoint_state().items():
                 out["case_" + k] = np.asarray(v)
@@ -236,6 +244,9 @@ def restore(case, path):
     b, m, ti = s.backend, s.mesh, s.time_integrator
     z = read_checkpoint(path)
     stats = getattr(case, "stats", None)
+    spectra = getattr(case, "spectra", None)
+    if spectra is not None and not spectra.cfg.active:
+        spectra = None
     # 2. does it fit?
     if int(z["precision"]) != REAL_BYTES:
         raise _differs("precision (bytes per real)", int(z["precision"]), REAL_BYTES)
@@ -271,6 +282,11 @@ def restore(case, path):
     if stats is not None and stats.cfg.active:
         if int(z.get("stats_profile_dir", -1)) != int(stats.cfg.profile_dir or 0):
             raise _differs("stats_profile_dir", int(z.get("stats_profile_dir", -1)), int(stats.cfg.profile_dir or 0))
+    if spectra is not None:
+        from .spectra import mean_from_state
+        if "spectra_sample_count" not in z:
+            raise X3dError("restore: this run samples spectra, the checkpoint holds none")
+        mean_from_state(z, spectra.cfg.mode, spectra.cfg.fields)  # (raises on another mode or other fields)
     # 3. upload, 4. the checksums of what arrived, one host wait
     n = int(np.prod(dims))
     data, off, total = b.checkpoint_layout(len(names), n)
@@ -302,6 +318,8 @@ def restore(case, path):
         if profile:
             stats.load_state_dict(z)
         stats.sample_count = int(z["stats_sample_count"])
+    if spectra is not None:
+        spectra.load_state_dict(z)
     case.load_checkpoint_state({k[5:]: v for k, v in z.items() if k.startswith("case_")})
     case.restarted = True
     return s.current_iter
