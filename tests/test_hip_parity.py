@@ -832,7 +832,8 @@ def test_fft512_strided_passes_and_fused_z_pass():
     """ny = nz = 512 switches the single-rank Poisson solver to its own strided 512-point FFT kernels
     (csrc/fft512.hip: y pass, and z forward + process_spectral_000 + z backward in one kernel).
     (1) fft_forward against numpy's FFT, (2) the fused solve against the unfused hooks and against
-    the rocFFT-only path (X3D_NO_FFT512=1) on the same input, (3) the oracle's spectral operator."""
+    the rocFFT-only path (X3D_NO_FFT512=1) and the tile branch of the fused pass (X3D_NO_RWT=1) on the same input,
+    (3) the oracle's spectral operator."""
     import os
     import subprocess
     import sys
@@ -863,12 +864,15 @@ def test_fft512_strided_passes_and_fused_z_pass():
     om = orc.Mesh(list(dims), [1, 1, 1], [twopi] * 3, ["periodic"] * 2, ["periodic"] * 2, ["periodic"] * 2)
     osol = orc.Solver(om, poisson="FFT").poisson_fft.solve(f)
     assert relerr(fused, osol) < 1e-11
-    if os.environ.get("X3D_NO_FFT512") != "1":  # same test on the rocFFT-only path
+    if os.environ.get("X3D_NO_FFT512") != "1" and os.environ.get("X3D_NO_RWT") != "1":
+        # same test on the rocFFT-only path, and with the fused z pass dividing in its row-cooperative layout (the
+        # tile branch of k_fft512<2>, which no size takes by default)
         np.save("/tmp/x3d_fft512_fused.npy", fused)
-        r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-x", "-q", "-m", "gpu", "-k",
-                            "fft512_strided"], env=dict(os.environ, X3D_NO_FFT512="1"), capture_output=True,
-                           text=True, timeout=900)
-        assert r.returncode == 0, r.stdout[-3000:]
+        for switch in ("X3D_NO_FFT512", "X3D_NO_RWT"):
+            r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-x", "-q", "-m", "gpu", "-k",
+                                "fft512_strided"], env=dict(os.environ, **{switch: "1"}), capture_output=True,
+                               text=True, timeout=900)
+            assert r.returncode == 0, (switch, r.stdout[-3000:])
     else:
         other = np.load("/tmp/x3d_fft512_fused.npy")
         assert relerr(fused, other) < 1e-12

@@ -11,12 +11,14 @@
 // register layout.  For the z axis the forward transform, the spectral division and the backward
 // transform are done in ONE kernel: the spectrum is read once and written once (2 passes instead
 // of 6 + the 1.5 of a separate process_spectral_000).
-#include "common.h"
+#include "fft_util.h"
 
 #include "fft512_core.h"
+#include "spectral000.h"
 
 struct Spec000 {
-    const real_t *waves, *ax, *bx, *ay, *by, *az, *bz;
+    const real_t *waves;
+    SpecAB t;
     int nx, ny, nz;
     const real_t *rwT;  // [ny][nxs][nz]: -1 / waves (0 where waves < 1e-16), z fastest; null: use waves
 };
@@ -77,11 +79,11 @@ __global__ void __launch_bounds__(64 * NP, 16 / NP)
         const int i = i0 + w, j = blockIdx.y;
         if (i < nxs) {
             // fixed over the pencil: the x mode and the rows' other index (y; ZH: kz); per point: the axis (z; ZH: y)
-            const real_t a_o = ZH ? sp.az[j] : sp.ay[j], b_o = ZH ? sp.bz[j] : sp.by[j];
+            const real_t a_o = ZH ? sp.t.az[j] : sp.t.ay[j], b_o = ZH ? sp.t.bz[j] : sp.t.by[j];
             const bool f_o = ZH ? false : (j + 1) > sp.ny / 2 + 1;
-            const real_t axi = sp.ax[i], bxi = sp.bx[i];
+            const real_t axi = sp.t.ax[i], bxi = sp.t.bx[i];
             const bool fx = ZH && (i + 1) > sp.nx / 2 + 1;
-            const real_t *__restrict__ a_ax = ZH ? sp.ay : sp.az, *__restrict__ b_ax = ZH ? sp.by : sp.bz;
+            const real_t *__restrict__ a_ax = ZH ? sp.t.ay : sp.t.az, *__restrict__ b_ax = ZH ? sp.t.by : sp.t.bz;
             const int n_ax = ZH ? sp.ny : sp.nz;
             const real_t rn = 1.0 / sp.nx / sp.ny / sp.nz;
             const real_t *__restrict__ rwp = sp.rwT + ((size_t)j * nxs + i) * 512;
@@ -91,29 +93,12 @@ __global__ void __launch_bounds__(64 * NP, 16 / NP)
                 real_t div_r = a[kk].x * rn, div_c = a[kk].y * rn;
                 const real_t a_k = a_ax[k], b_k = b_ax[k];
                 const bool f_k = (k + 1) > n_ax / 2 + 1;
-                const real_t azk = ZH ? a_o : a_k, bzk = ZH ? b_o : b_k, ayj = ZH ? a_k : a_o, byj = ZH ? b_k : b_o;
-                const bool fz = ZH ? f_o : f_k, fy = ZH ? f_k : f_o;
-                real_t tr, tc;
-                tr = div_r; tc = div_c;
-                div_r = tr * bzk + tc * azk; div_c = tc * bzk - tr * azk;
-                if (fz) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-                if (fy) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * bxi + tc * axi; div_c = tc * bxi - tr * axi;
-                if (fx) { div_r = -div_r; div_c = -div_c; }
+                const Spec000Mode md = ZH ? Spec000Mode{a_o, b_o, a_k, b_k, axi, bxi, f_o, f_k, fx}
+                                         : Spec000Mode{a_k, b_k, a_o, b_o, axi, bxi, f_k, f_o, fx};
+                spec000_forward(div_r, div_c, md);
                 const real_t rw = rwp[k];
                 div_r = div_r * rw; div_c = div_c * rw;
-                tr = div_r; tc = div_c;
-                div_r = tr * bzk - tc * azk; div_c = -tc * bzk - tr * azk;
-                if (fz) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-                if (fy) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * bxi + tc * axi; div_c = -tc * bxi + tr * axi;
-                if (fx) { div_r = -div_r; div_c = -div_c; }
+                spec000_backward(div_r, div_c, md);
                 a[kk] = make_real2(div_r, div_c);
             }
         }
@@ -126,7 +111,7 @@ __global__ void __launch_bounds__(64 * NP, 16 / NP)
         __syncthreads();
         const int j = blockIdx.y, i = i0 + m;
         if (valid) {
-            const real_t ayj = sp.ay[j], byj = sp.by[j], axi = sp.ax[i], bxi = sp.bx[i];
+            const real_t ayj = sp.t.ay[j], byj = sp.t.by[j], axi = sp.t.ax[i], bxi = sp.t.bx[i];
             // the reference divides by nx, ny, nz and by waves per element (8 FP64 divisions); here one
             // reciprocal of the product and one of waves: <= 2 ulp apart, far inside the parity tolerance
             const real_t rn = 1.0 / sp.nx / sp.ny / sp.nz;
@@ -135,29 +120,12 @@ __global__ void __launch_bounds__(64 * NP, 16 / NP)
             for (int it = 0; it < 8; it++) {
                 const int k = it * 64 + r;
                 real2_t v = tile[m * FP + k];
-                // src/backend/omp/kernels/spectral_processing.f90:36-99, same order as k_process_spectral_000
                 real_t div_r = v.x * rn, div_c = v.y * rn;
-                const real_t azk = sp.az[k], bzk = sp.bz[k];
-                const bool fz = (k + 1) > sp.nz / 2 + 1;
-                real_t tr, tc;
-                tr = div_r; tc = div_c;
-                div_r = tr * bzk + tc * azk; div_c = tc * bzk - tr * azk;
-                if (fz) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-                if (fy) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * bxi + tc * axi; div_c = tc * bxi - tr * axi;
+                const Spec000Mode md{sp.t.az[k], sp.t.bz[k], ayj, byj, axi, bxi, (k + 1) > sp.nz / 2 + 1, fy, false};
+                spec000_forward(div_r, div_c, md);
                 const real_t rw = rw8[it];
                 div_r = div_r * rw; div_c = div_c * rw;
-                tr = div_r; tc = div_c;
-                div_r = tr * bzk - tc * azk; div_c = -tc * bzk - tr * azk;
-                if (fz) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-                if (fy) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * bxi + tc * axi; div_c = -tc * bxi + tr * axi;
+                spec000_backward(div_r, div_c, md);
                 tile[m * FP + k] = make_real2(div_r, div_c);
             }
         }
@@ -208,7 +176,7 @@ __device__ __forceinline__ void dft_small(real2_t (&v)[8])
 
 struct SpecSlab {
     const real_t *waves;  // this part's -1 / waves [W][nz], z fastest (0 where waves < 1e-16)
-    const real_t *ax, *bx, *ay, *by, *az, *bz;
+    SpecAB t;
     int nx, ny, nz, nxs, yoff;
     int xoff;  // YL only
 };
@@ -281,11 +249,11 @@ __global__ void __launch_bounds__(64 * WV, 16 / WV)
         if (wl < W) {
             const int i = (int)(wl % sp.nxs) + (YL ? sp.xoff : 0), j = (int)(wl / sp.nxs) + sp.yoff;
             // fixed over the pencil: the x mode and the second mode index (y; YL: kz); per point: the long axis (z; YL: y)
-            const real_t a_o = YL ? sp.az[j] : sp.ay[j], b_o = YL ? sp.bz[j] : sp.by[j];
+            const real_t a_o = YL ? sp.t.az[j] : sp.t.ay[j], b_o = YL ? sp.t.bz[j] : sp.t.by[j];
             const bool f_o = YL ? false : (j + 1) > sp.ny / 2 + 1;
-            const real_t axi = sp.ax[i], bxi = sp.bx[i];
+            const real_t axi = sp.t.ax[i], bxi = sp.t.bx[i];
             const bool fx = YL && (i + 1) > sp.nx / 2 + 1;
-            const real_t *__restrict__ a_ax = YL ? sp.ay : sp.az, *__restrict__ b_ax = YL ? sp.by : sp.bz;
+            const real_t *__restrict__ a_ax = YL ? sp.t.ay : sp.t.az, *__restrict__ b_ax = YL ? sp.t.by : sp.t.bz;
             const int n_ax = YL ? sp.ny : sp.nz;
             const real_t *__restrict__ wv = sp.waves + wl * n_ax;
             const real_t rn = 1.0 / sp.nx / sp.ny / sp.nz;
@@ -295,29 +263,12 @@ __global__ void __launch_bounds__(64 * WV, 16 / WV)
                 real_t div_r = a[kk].x * rn, div_c = a[kk].y * rn;
                 const real_t a_k = a_ax[k], b_k = b_ax[k];
                 const bool f_k = (k + 1) > n_ax / 2 + 1;
-                const real_t azk = YL ? a_o : a_k, bzk = YL ? b_o : b_k, ayj = YL ? a_k : a_o, byj = YL ? b_k : b_o;
-                const bool fz = YL ? f_o : f_k, fy = YL ? f_k : f_o;
-                real_t tr, tc;
-                tr = div_r; tc = div_c;
-                div_r = tr * bzk + tc * azk; div_c = tc * bzk - tr * azk;
-                if (fz) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-                if (fy) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * bxi + tc * axi; div_c = tc * bxi - tr * axi;
-                if (fx) { div_r = -div_r; div_c = -div_c; }
+                const Spec000Mode md = YL ? Spec000Mode{a_o, b_o, a_k, b_k, axi, bxi, f_o, f_k, fx}
+                                         : Spec000Mode{a_k, b_k, a_o, b_o, axi, bxi, f_k, f_o, fx};
+                spec000_forward(div_r, div_c, md);
                 const real_t rw = wv[k];  // (-1 / waves)
                 div_r = div_r * rw; div_c = div_c * rw;
-                tr = div_r; tc = div_c;
-                div_r = tr * bzk - tc * azk; div_c = -tc * bzk - tr * azk;
-                if (fz) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-                if (fy) { div_r = -div_r; div_c = -div_c; }
-                tr = div_r; tc = div_c;
-                div_r = tr * bxi + tc * axi; div_c = -tc * bxi + tr * axi;
-                if (fx) { div_r = -div_r; div_c = -div_c; }
+                spec000_backward(div_r, div_c, md);
                 a[kk] = make_real2(div_r, div_c);
             }
         }
@@ -380,11 +331,6 @@ __global__ void __launch_bounds__(256) k_radix_peers(real2_t *R, long W)
 
 static real2_t *g_tw = nullptr;  // W512^k = exp(-2 pi i k / 512), first half, shared by all plans
 
-// R: one part of the received array [512 N][W]; waves: that part's [W][512 N]; returns *done = false when the
-// sizes are not served (N not 1, 2, 4, 8)
-int x3d_fft512_peers(x3d_backend *b, real2_t *R, long W, int npeers, const real_t *waves, const real_t *ab, int nx, int ny,
-                     int nz, int nxs, int yoff, bool *done);
-
 template <int MODE, int NP>
 static int launch512(x3d_backend *b, real2_t *c, long stride_axis, long stride_other, int nxs, int nother,
                      const Spec000 &sp, real2_t *xbuf, int ys, int ysc)
@@ -403,10 +349,11 @@ int x3d_fft512_run_zh(x3d_backend *b, real2_t *c, long px, int kz0, int nkz, con
                       int ny, int nz)
 {
     X3D_REQUIRE(g_tw && nx == 512 && ny == 512 && nz == 512 && rwZ, "x3d_fft512_run_zh: 512^3 only");
-    const real_t *ax = ab, *bx = ax + nx, *ay = bx + nx, *by = ay + ny, *az = by + ny, *bz = az + nz;
     // the planes kz0 .. kz0 + nkz - 1 (the kernel numbers its rows' other index from 0)
     c += (long)kz0 * ny * px;
-    const Spec000 sp{nullptr, ax, bx, ay, by, az + kz0, bz + kz0, nx, ny, nz, rwZ + (size_t)kz0 * 512 * 512};
+    SpecAB t = spec_ab_view(ab, nx, ny, nz);
+    t.az += kz0; t.bz += kz0;
+    const Spec000 sp{nullptr, t, nx, ny, nz, rwZ + (size_t)kz0 * 512 * 512};
     ProfScope ps(b, X3D_K_SPECTRAL, 1);
     const int lds = sizeof(real2_t) * (8 * FP + 256);
     X3D_LDS_OPTIN(b, (k_fft512<2, 8, true>));
@@ -432,9 +379,6 @@ int x3d_fft512_init()
     return 0;
 }
 
-// axis: 1 = y (ny must be 512), 2 = z (nz must be 512); mode 0 fwd, 1 bwd, 2 fused z pass
-int x3d_fft512_run_x(x3d_backend *b, real2_t *c, int nxs, int ny, int nz, int axis, int mode, const real_t *waves,
-                     const real_t *ab, int nx, real2_t *xbuf, int ys, int ysc);
 static const real_t *g_rwT = nullptr;  // set by x3d_fft512_set_rwT for the next fused z pass (poisson.hip)
 void x3d_fft512_set_rwT(const real_t *rwT) { g_rwT = rwT; }
 
@@ -456,10 +400,7 @@ int x3d_fft512_run_x(x3d_backend *b, real2_t *c, int nxs, int ny, int nz, int ax
     X3D_REQUIRE(!xbuf || (axis == 1 && mode != 2 && ys > 0 && 512 % ys == 0 && ysc > 0 && ys % ysc == 0),
                 "x3d_fft512_run: bad slab exchange");
     Spec000 sp{};
-    if (mode == 2) {
-        const real_t *ax = ab, *bx = ax + nx, *ay = bx + nx, *by = ay + ny, *az = by + ny, *bz = az + nz;
-        sp = Spec000{waves, ax, bx, ay, by, az, bz, nx, ny, nz, g_rwT};
-    }
+    if (mode == 2) sp = Spec000{waves, spec_ab_view(ab, nx, ny, nz), nx, ny, nz, g_rwT};
     // the y pass on rows of 256 B (16 modes, one 16-wave workgroup per CU), the z pass on rows of 128 B (8 modes) --
     // measured: y pass 0.53 vs 0.58 ms with 16 modes, z pass 0.90 vs 0.96 with 8
     const bool w16 = axis == 1;
@@ -569,8 +510,7 @@ int x3d_fft512_peers(x3d_backend *b, real2_t *R, long W, int npeers, const real_
 {
     *done = false;
     if (!g_tw || nz != 512 * npeers || !(npeers == 1 || npeers == 2 || npeers == 4 || npeers == 8)) return 0;
-    const real_t *ax = ab, *bx = ax + nx, *ay = bx + nx, *by = ay + ny, *az = by + ny, *bz = az + nz;
-    const SpecSlab sp{waves, ax, bx, ay, by, az, bz, nx, ny, nz, nxs, yoff, 0};
+    const SpecSlab sp{waves, spec_ab_view(ab, nx, ny, nz), nx, ny, nz, nxs, yoff, 0};
     if (int rc = peers_run<false>(b, R, W, npeers, sp)) return rc;
     *done = true;
     return 0;
@@ -583,8 +523,7 @@ int x3d_fft512_peers_yl(x3d_backend *b, real2_t *R, long W, int npeers, const re
 {
     X3D_REQUIRE(g_tw && ny == 512 * npeers && (npeers == 1 || npeers == 2 || npeers == 4 || npeers == 8),
                 "x3d_fft512_peers_yl: %d chunks of 512 rows along y on 1, 2, 4 or 8 ranks", npeers);
-    const real_t *ax = ab, *bx = ax + nx, *ay = bx + nx, *by = ay + ny, *az = by + ny, *bz = az + nz;
-    const SpecSlab sp{rw, ax, bx, ay, by, az, bz, nx, ny, nz, xs, kz0, xoff};
+    const SpecSlab sp{rw, spec_ab_view(ab, nx, ny, nz), nx, ny, nz, xs, kz0, xoff};
     switch (part) {  // 0: forward + division + inverse; 1 / 2 / 3: forward / inverse / division alone (the hooks)
     case 0: return peers_run<true, 0>(b, R, W, npeers, sp);
     case 1: return peers_run<true, 1>(b, R, W, npeers, sp);

@@ -19,19 +19,8 @@
 // xy exchange, the y transform and the yz exchange of a group run beside the transfers of the others; the
 // reference's 2decomp&FFT transposes are blocking (src/backend/omp/poisson_fft.f90:99-137).  Exchange buffers of a
 // group: [part][peer][zp][..][..], a peer's chunk contiguous (x3d_pfft_part_layout).
-#include <hipfft/hipfft.h>
-
-#include "common.h"
-
-#define X3D_FFT(expr)                                                                          \
-    do {                                                                                       \
-        hipfftResult r_ = (expr);                                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                                            \
-            x3d_set_error("%s failed: hipfft error %d (%s:%d)", #expr, (int)r_, __FILE__,      \
-                          __LINE__);                                                           \
-            return 3;                                                                          \
-        }                                                                                      \
-    } while (0)
+#include "fft_util.h"
+#include "spectral000.h"
 
 static inline int share(int n, int p, int r) { return n / p + (r < n % p ? 1 : 0); }
 static inline int share_off(int n, int p, int r) { return r * (n / p) + (r < n % p ? r : n % p); }
@@ -150,28 +139,12 @@ __global__ void __launch_bounds__(256)
     const size_t idx = ((size_t)il * ys + jl) * nz + k;
     real2_t v = c[idx];
     real_t div_r = v.x / nx / ny / nz, div_c = v.y / nx / ny / nz;
-    const real_t azk = az[k], bzk = bz[k], ayj = ay[j], byj = by[j], axi = ax[i], bxi = bx[i];
-    const bool fz = (k + 1) > nz / 2 + 1, fy = (j + 1) > ny / 2 + 1;
-    real_t tr, tc;
-    tr = div_r; tc = div_c;
-    div_r = tr * bzk + tc * azk; div_c = tc * bzk - tr * azk;
-    if (fz) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-    if (fy) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * bxi + tc * axi; div_c = tc * bxi - tr * axi;
+    const Spec000Mode md{az[k], bz[k], ay[j], by[j], ax[i], bx[i], (k + 1) > nz / 2 + 1, (j + 1) > ny / 2 + 1, false};
+    spec000_forward(div_r, div_c, md);
     const real_t wv = waves[idx];
     if (wv < 1.e-16) { div_r = 0.0; div_c = 0.0; }
     else { div_r = -div_r / wv; div_c = -div_c / wv; }
-    tr = div_r; tc = div_c;
-    div_r = tr * bzk - tc * azk; div_c = -tc * bzk - tr * azk;
-    if (fz) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-    if (fy) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * bxi + tc * axi; div_c = -tc * bxi + tr * axi;
+    spec000_backward(div_r, div_c, md);
     c[idx] = make_real2(div_r, div_c);
 }
 
@@ -212,14 +185,11 @@ extern "C" int x3d_pfft_create_parts(x3d_backend *b, x3d_pfft **out, const int n
     X3D_HIP(hipMalloc(&p->c1, sizeof(real2_t) * n1));
     X3D_HIP(hipMalloc(&p->c2, sizeof(real2_t) * n2));
     X3D_HIP(hipMalloc(&p->waves, sizeof(real_t) * n2));
-    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * 2 * ((size_t)p->nx + p->ny + p->nz)));
+    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * spec_ab_elems(p->nx, p->ny, p->nz)));
     int nxv[1] = {p->nx}, nyv[1] = {p->ny}, nzv[1] = {p->nz};
     size_t ws[4] = {0, 0, 0, 0};
     hipfftHandle *pl[4] = {&p->plan_r2c, &p->plan_c2r, &p->plan_y, &p->plan_z};
-    for (int i = 0; i < 4; i++) {
-        X3D_FFT(hipfftCreate(pl[i]));
-        X3D_FFT(hipfftSetAutoAllocation(*pl[i], 0));
-    }
+    if (int rc = fft_plans_create(pl, 4)) return rc;
     int rembed[1] = {b->nxp}, cembed[1] = {p->nxs};
     X3D_FFT(hipfftMakePlanMany(p->plan_r2c, 1, nxv, rembed, 1, b->nxp, cembed, 1, p->nxs, X3D_FFT_R2C,
                                p->yl * p->zp, &ws[0]));
@@ -227,10 +197,7 @@ extern "C" int x3d_pfft_create_parts(x3d_backend *b, x3d_pfft **out, const int n
                                p->yl * p->zp, &ws[1]));
     X3D_FFT(hipfftMakePlanMany(p->plan_y, 1, nyv, nyv, 1, p->ny, nyv, 1, p->ny, X3D_FFT_C2C, p->zp * p->xs, &ws[2]));
     X3D_FFT(hipfftMakePlanMany(p->plan_z, 1, nzv, nzv, 1, p->nz, nzv, 1, p->nz, X3D_FFT_C2C, p->xs * p->ys, &ws[3]));
-    size_t wmax = 0;
-    for (int i = 0; i < 4; i++) wmax = ws[i] > wmax ? ws[i] : wmax;
-    if (wmax) X3D_HIP(hipMalloc(&p->work, wmax));
-    for (int i = 0; i < 4; i++) X3D_FFT(hipfftSetWorkArea(*pl[i], p->work));
+    if (int rc = fft_plans_share_work(pl, ws, nullptr, 4, &p->work)) return rc;
     *out = p;
     return 0;
 }
@@ -239,8 +206,9 @@ extern "C" int x3d_pfft_destroy(x3d_pfft *p)
 {
     X3D_RANGE(__func__);
     if (!p) return 0;
-    hipfftDestroy(p->plan_r2c); hipfftDestroy(p->plan_c2r); hipfftDestroy(p->plan_y); hipfftDestroy(p->plan_z);
-    hipFree(p->c0); hipFree(p->c1); hipFree(p->c2); hipFree(p->waves); hipFree(p->ab); hipFree(p->work);
+    hipfftHandle *pl[4] = {&p->plan_r2c, &p->plan_c2r, &p->plan_y, &p->plan_z};
+    fft_plans_destroy(pl, 4, p->work);
+    hipFree(p->c0); hipFree(p->c1); hipFree(p->c2); hipFree(p->waves); hipFree(p->ab);
     delete p;
     return 0;
 }
@@ -266,14 +234,7 @@ extern "C" int x3d_pfft_set_waves(x3d_pfft *p, const real_t *waves_re, const rea
     X3D_REQUIRE(p && waves_re && ax && bx && ay && by && az && bz, "null argument");
     const size_t n2 = (size_t)p->xs * p->ys * p->nz;
     X3D_HIP(hipMemcpy(p->waves, waves_re, sizeof(real_t) * n2, hipMemcpyHostToDevice));
-    real_t *d = p->ab;
-    const real_t *src[6] = {ax, bx, ay, by, az, bz};
-    const int len[6] = {p->nx, p->nx, p->ny, p->ny, p->nz, p->nz};
-    for (int i = 0; i < 6; i++) {
-        X3D_HIP(hipMemcpy(d, src[i], sizeof(real_t) * len[i], hipMemcpyHostToDevice));
-        d += len[i];
-    }
-    return 0;
+    return spec_ab_upload(p->ab, p->nx, p->ny, p->nz, p->nx, ax, bx, ay, by, az, bz);
 }
 
 // ---- local stages on the planes [z0, z0 + nzp_) of this rank (a whole number of groups)
@@ -573,12 +534,11 @@ extern "C" int x3d_pfft_postprocess_000(x3d_pfft *p)
     X3D_RANGE(__func__);
     X3D_REQUIRE(p, "null argument");
     if (p->xs == 0 || p->ys == 0) return 0;
-    const real_t *ax = p->ab, *bx = ax + p->nx, *ay = bx + p->nx, *by = ay + p->ny, *az = by + p->ny,
-                 *bz = az + p->nz;
+    const SpecAB t = spec_ab_view(p->ab, p->nx, p->ny, p->nz);
     dim3 grid((p->nz + 255) / 256, p->ys, p->xs);
     ProfScope ps(p->b, X3D_K_SPECTRAL);
     hipLaunchKernelGGL(k_process_spectral_000_z, grid, dim3(256), 0, p->b->stream, p->c2, p->waves, p->xs, p->ys,
-                       p->nz, p->xoff, p->yoff, p->nx, p->ny, ax, bx, ay, by, az, bz);
+                       p->nz, p->xoff, p->yoff, p->nx, p->ny, t.ax, t.bx, t.ay, t.by, t.az, t.bz);
     X3D_HIP(hipGetLastError());
     return 0;
 }

@@ -8,26 +8,10 @@
 //       r2c / c2r, forward e^{-i}, spectral array (nx/2+1, ny, nz)
 //   src/backend/omp/kernels/spectral_processing.f90:7-106 process_spectral_000
 //   (CUDA analogue: src/backend/cuda/poisson_fft.f90:618-777, kernels/spectral_processing.f90:127-224)
-#include <hipfft/hipfft.h>
-
-#include "common.h"
-
+#include "fft_util.h"
 #include "poisson_priv.h"
+#include "spectral000.h"
 int x3d_proxy_hook(x3d_poisson *p, int which, real_t *f);  // zfirst.hip
-
-int x3d_fft512_init();
-int x3d_fft512_run(x3d_backend *b, real2_t *c, int nxs, int ny, int nz, int axis, int mode, const real_t *waves,
-                   const real_t *ab, int nx);
-
-#define X3D_FFT(expr)                                                                          \
-    do {                                                                                       \
-        hipfftResult r_ = (expr);                                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                                            \
-            x3d_set_error("%s failed: hipfft error %d (%s:%d)", #expr, (int)r_, __FILE__,      \
-                          __LINE__);                                                           \
-            return 3;                                                                          \
-        }                                                                                      \
-    } while (0)
 
 // pad columns [nxm, nxs) of a pitched array of doubles <- v
 __global__ void k_fill_pad(real_t *__restrict__ a, size_t rows, int nxm, int nxs, real_t v)
@@ -60,34 +44,12 @@ __global__ void __launch_bounds__(256)
     real2_t v = c[idx];
     // normalisation (:36-37): the three divisions of the reference, same order
     real_t div_r = v.x / nx / ny / nz, div_c = v.y / nx / ny / nz;
-    const real_t azk = az[k], bzk = bz[k], ayj = ay[j], byj = by[j], axi = ax[i], bxi = bx[i];
-    const bool fz = (k + 1) > nz / 2 + 1, fy = (j + 1) > ny / 2 + 1;
-    real_t tr, tc;
-    tr = div_r; tc = div_c;                       // z forward (:46-51)
-    div_r = tr * bzk + tc * azk;
-    div_c = tc * bzk - tr * azk;
-    if (fz) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;                       // y forward (:54-59)
-    div_r = tr * byj + tc * ayj;
-    div_c = tc * byj - tr * ayj;
-    if (fy) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;                       // x forward (:62-65)
-    div_r = tr * bxi + tc * axi;
-    div_c = tc * bxi - tr * axi;
+    const Spec000Mode md{az[k], bz[k], ay[j], by[j], ax[i], bx[i], (k + 1) > nz / 2 + 1, (j + 1) > ny / 2 + 1, false};
+    spec000_forward(div_r, div_c, md);
     const real_t wv = waves[idx];                 // real part == imaginary part (:68-76)
     if (wv < 1.e-16) { div_r = 0.0; div_c = 0.0; }
     else { div_r = -div_r / wv; div_c = -div_c / wv; }
-    tr = div_r; tc = div_c;                       // z backward (:80-85)
-    div_r = tr * bzk - tc * azk;
-    div_c = -tc * bzk - tr * azk;
-    if (fz) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;                       // y backward (:88-93)
-    div_r = tr * byj + tc * ayj;
-    div_c = tc * byj - tr * ayj;
-    if (fy) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;                       // x backward (:96-99)
-    div_r = tr * bxi + tc * axi;
-    div_c = -tc * bxi + tr * axi;
+    spec000_backward(div_r, div_c, md);
     c[idx] = make_real2(div_r, div_c);
 }
 
@@ -121,32 +83,20 @@ extern "C" int x3d_poisson_create(x3d_backend *b, x3d_poisson **out, const int n
                            p->nxs, 1.0);
         X3D_HIP(hipDeviceSynchronize());
     }
-    const size_t nab = 2 * ((size_t)n[0] + n[1] + n[2]);
-    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * nab));
-    real_t *d = p->ab;
-    const real_t *src[6] = {ax, bx, ay, by, az, bz};
-    const int len[6] = {n[0], n[0], n[1], n[1], n[2], n[2]};
-    for (int i = 0; i < 6; i++) {
-        X3D_HIP(hipMemcpy(d, src[i], sizeof(real_t) * len[i], hipMemcpyHostToDevice));
-        d += len[i];
-    }
+    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * spec_ab_elems(n[0], n[1], n[2])));
+    if (int rc = spec_ab_upload(p->ab, n[0], n[1], n[2], n[0], ax, bx, ay, by, az, bz)) return rc;
     // real side lives in the pitched block: embed = {nzp, nyp, nxp}; spectral side dense
     int dims[3] = {p->nz, p->ny, p->nx};
     int rembed[3] = {b->nzp, b->nyp, b->nxp};
     int cembed[3] = {p->nz, p->ny, p->nxs};
-    X3D_FFT(hipfftCreate(&p->plan_fw));
-    X3D_FFT(hipfftCreate(&p->plan_bw));
-    X3D_FFT(hipfftSetAutoAllocation(p->plan_fw, 0));
-    X3D_FFT(hipfftSetAutoAllocation(p->plan_bw, 0));
-    size_t ws_fw = 0, ws_bw = 0;
+    hipfftHandle *pl[2] = {&p->plan_fw, &p->plan_bw};
+    size_t ws[2] = {0, 0};
+    if (int rc = fft_plans_create(pl, 2)) return rc;
     X3D_FFT(hipfftMakePlanMany(p->plan_fw, 3, dims, rembed, 1, (int)b->nblock, cembed, 1, (int)ns, X3D_FFT_R2C, 1,
-                               &ws_fw));
+                               &ws[0]));
     X3D_FFT(hipfftMakePlanMany(p->plan_bw, 3, dims, cembed, 1, (int)ns, rembed, 1, (int)b->nblock, X3D_FFT_C2R, 1,
-                               &ws_bw));
-    p->work_size = ws_fw > ws_bw ? ws_fw : ws_bw;
-    if (p->work_size) X3D_HIP(hipMalloc(&p->work, p->work_size));
-    X3D_FFT(hipfftSetWorkArea(p->plan_fw, p->work));
-    X3D_FFT(hipfftSetWorkArea(p->plan_bw, p->work));
+                               &ws[1]));
+    if (int rc = fft_plans_share_work(pl, ws, nullptr, 2, &p->work, &p->work_size)) return rc;
     const char *no512 = getenv("X3D_NO_FFT512");
     if (p->ny == 512 && p->nz == 512 && !(no512 && no512[0] == '1')) {
         // batched 1-D r2c / c2r along x straight on the pitched block (rows nxp apart -> nxs complex)
@@ -194,9 +144,6 @@ extern "C" int x3d_poisson_destroy(x3d_poisson *p)
     return 0;
 }
 
-int x3d_fft512_r2c(x3d_backend *b, real2_t *c, const real_t *f, long nrows, long frow, long crow);
-void x3d_fft512_set_rwT(const real_t *rwT);
-
 // x pass of the fast path: real rows (nxp apart) -> nxs complex modes
 static int x_forward_512(x3d_poisson *p, const real_t *f)
 {
@@ -231,12 +178,11 @@ extern "C" int x3d_poisson_postprocess_000(x3d_poisson *p)
     X3D_REQUIRE(p, "x3d_poisson_postprocess_000: null argument");
     if (x3d_lazy_active(p->b)) return x3d_lazy_fft(p->b, 1, p, nullptr);
     if (p->ext_middle) return x3d_proxy_hook(p, 1, nullptr);
-    const real_t *ax = p->ab, *bx = ax + p->nx, *ay = bx + p->nx, *by = ay + p->ny, *az = by + p->ny,
-                 *bz = az + p->nz;
+    const SpecAB t = spec_ab_view(p->ab, p->nx, p->ny, p->nz);
     dim3 grid((p->nxs + 255) / 256, p->ny, p->nz);
     ProfScope ps(p->b, X3D_K_SPECTRAL);
     hipLaunchKernelGGL(k_process_spectral_000, grid, dim3(256), 0, p->b->stream, p->c, p->waves, p->nxs, p->ny,
-                       p->nz, p->nx, ax, bx, ay, by, az, bz);
+                       p->nz, p->nx, t.ax, t.bx, t.ay, t.by, t.az, t.bz);
     X3D_HIP(hipGetLastError());
     return 0;
 }
@@ -452,16 +398,15 @@ extern "C" int x3d_poisson_postprocess_011(x3d_poisson *p)
     X3D_LAZY_FLUSH(p->b);
     X3D_LAZY_EAGER(p->b);
     X3D_REQUIRE(!p->stretched, "x3d_poisson_postprocess_011: uniform grids only");
-    const real_t *ax = p->ab, *bx = ax + p->nx, *ay = bx + p->nx, *by = ay + p->ny, *az = by + p->ny,
-                 *bz = az + p->nz;
+    const SpecAB t = spec_ab_view(p->ab, p->nx, p->ny, p->nz);
     ProfScope ps(p->b, X3D_K_SPECTRAL);
     hipStream_t st = p->b->stream;
     dim3 gy = spectral_010_grid(p->nxs, p->ny, p->nz), gz((p->nxs + 255) / 256, p->ny, p->nz / 2 + 1);
-    hipLaunchKernelGGL((k_spectral_010<0, false>), gy, dim3(256), 0, st, p->c, p->waves, p->nxs, p->ny, p->nz, p->nx, 0, ax,
-                       bx, ay, by, az, bz);
-    hipLaunchKernelGGL(k_spectral_pair_z, gz, dim3(256), 0, st, p->c, p->waves, p->nxs, p->ny, p->nz, p->nx, az, bz);
-    hipLaunchKernelGGL((k_spectral_010<1, false>), gy, dim3(256), 0, st, p->c, p->waves, p->nxs, p->ny, p->nz, p->nx, 0, ax,
-                       bx, ay, by, az, bz);
+    hipLaunchKernelGGL((k_spectral_010<0, false>), gy, dim3(256), 0, st, p->c, p->waves, p->nxs, p->ny, p->nz, p->nx, 0, t.ax,
+                       t.bx, t.ay, t.by, t.az, t.bz);
+    hipLaunchKernelGGL(k_spectral_pair_z, gz, dim3(256), 0, st, p->c, p->waves, p->nxs, p->ny, p->nz, p->nx, t.az, t.bz);
+    hipLaunchKernelGGL((k_spectral_010<1, false>), gy, dim3(256), 0, st, p->c, p->waves, p->nxs, p->ny, p->nz, p->nx, 0, t.ax,
+                       t.bx, t.ay, t.by, t.az, t.bz);
     X3D_HIP(hipGetLastError());
     return 0;
 }

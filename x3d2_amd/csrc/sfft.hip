@@ -20,27 +20,8 @@
 //   --k_fft512 (y backward), loading from the exchange layout-->  C0  --rocFFT C2R x-->  f
 // ~19 field passes per solve against ~30 for the generic pencil solver (pfft.hip: contiguous-axis rocFFT
 // stages with pack / transpose passes around every exchange).
-#include <hipfft/hipfft.h>
-
-#include "common.h"
-
-#define X3D_FFT(expr)                                                                          \
-    do {                                                                                       \
-        hipfftResult r_ = (expr);                                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                                            \
-            x3d_set_error("%s failed: hipfft error %d (%s:%d)", #expr, (int)r_, __FILE__,      \
-                          __LINE__);                                                           \
-            return 3;                                                                          \
-        }                                                                                      \
-    } while (0)
-
-int x3d_fft512_init();
-int x3d_fft512_run_x(x3d_backend *b, real2_t *c, int nxs, int ny, int nz, int axis, int mode, const real_t *waves,
-                     const real_t *ab, int nx, real2_t *xbuf, int ys, int ysc);
-
-int x3d_fft512_r2c(x3d_backend *b, real2_t *c, const real_t *f, long nrows, long frow, long crow);  // fft512.hip
-int x3d_fft512_peers(x3d_backend *b, real2_t *R, long W, int npeers, const real_t *waves, const real_t *ab, int nx, int ny,
-                     int nz, int nxs, int yoff, bool *done);  // fft512.hip
+#include "fft_util.h"
+#include "spectral000.h"
 
 struct x3d_sfft {
     x3d_backend *b;
@@ -55,26 +36,6 @@ struct x3d_sfft {
     real_t *waves, *ab;   // -1 / waves [ys][nxs][nz] (0 where waves < 1e-16); ax bx ay by az bz
     void *work;
 };
-
-// 32 x 32 tiles through LDS: src [nB][nA] (A contiguous) -> dst [nA][nB] (B contiguous), 512-byte rows both ways
-__global__ void __launch_bounds__(256)
-    k_sfft_transpose(real2_t *__restrict__ dst, const real2_t *__restrict__ src, int nA, int nB)
-{
-    __shared__ real2_t tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int a0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int bb = b0 + ty + 8 * r, aa = a0 + tx;
-        if (aa < nA && bb < nB) tile[ty + 8 * r][tx] = src[(long)bb * nA + aa];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int aa = a0 + ty + 8 * r, bb = b0 + tx;
-        if (aa < nA && bb < nB) dst[(long)aa * nB + bb] = tile[tx][ty + 8 * r];
-    }
-}
 
 // process_spectral_000 (src/backend/omp/kernels/spectral_processing.f90:7-106) on T[ys][nxs][nz] (z fastest):
 // y index offset = rz * ys (sp_st(2)), one thread per mode
@@ -92,27 +53,11 @@ __global__ void __launch_bounds__(256)
     real2_t v = c[idx];
     const real_t rn = 1.0 / nx / ny / nz;
     real_t div_r = v.x * rn, div_c = v.y * rn;
-    const real_t azk = az[k], bzk = bz[k], ayj = ay[j], byj = by[j], axi = ax[i], bxi = bx[i];
-    const bool fz = (k + 1) > nz / 2 + 1, fy = (j + 1) > ny / 2 + 1;
-    real_t tr, tc;
-    tr = div_r; tc = div_c;
-    div_r = tr * bzk + tc * azk; div_c = tc * bzk - tr * azk;
-    if (fz) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-    if (fy) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * bxi + tc * axi; div_c = tc * bxi - tr * axi;
+    const Spec000Mode md{az[k], bz[k], ay[j], by[j], ax[i], bx[i], (k + 1) > nz / 2 + 1, (j + 1) > ny / 2 + 1, false};
+    spec000_forward(div_r, div_c, md);
     const real_t rw = waves[idx];  // (-1 / waves, x3d_sfft_set_waves)
     div_r = div_r * rw; div_c = div_c * rw;
-    tr = div_r; tc = div_c;
-    div_r = tr * bzk - tc * azk; div_c = -tc * bzk - tr * azk;
-    if (fz) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * byj + tc * ayj; div_c = tc * byj - tr * ayj;
-    if (fy) { div_r = -div_r; div_c = -div_c; }
-    tr = div_r; tc = div_c;
-    div_r = tr * bxi + tc * axi; div_c = -tc * bxi + tr * axi;
+    spec000_backward(div_r, div_c, md);
     c[idx] = make_real2(div_r, div_c);
 }
 
@@ -155,23 +100,17 @@ extern "C" int x3d_sfft_create_parts(x3d_backend *b, x3d_sfft **out, const int n
     X3D_HIP(hipMemset(p->c0, 0, sizeof(real2_t) * n0));  // (the pad columns stay zero: the x transforms never write them)
     X3D_HIP(hipMalloc(&p->t, sizeof(real2_t) * (size_t)p->nz * p->ys * p->nxs));
     X3D_HIP(hipMalloc(&p->waves, sizeof(real_t) * (size_t)p->nz * p->ys * p->nxs));
-    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * 2 * ((size_t)p->nx + p->ny + p->nz)));
+    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * spec_ab_elems(p->nx, p->ny, p->nz)));
     int nn[1] = {p->nx}, re[1] = {b->nxp}, ce[1] = {p->nxs}, nzv[1] = {p->nz};
     const int batch = p->ny * p->zl, zstride = p->ysc * p->nxs;  // (z plan: one part at a time)
     hipfftHandle *pl[3] = {&p->plan_x_fw, &p->plan_x_bw, &p->plan_z};
     size_t ws[3] = {0, 0, 0};
-    for (int i = 0; i < 3; i++) {
-        X3D_FFT(hipfftCreate(pl[i]));
-        X3D_FFT(hipfftSetAutoAllocation(*pl[i], 0));
-    }
+    if (int rc = fft_plans_create(pl, 3)) return rc;
     X3D_FFT(hipfftMakePlanMany(p->plan_x_fw, 1, nn, re, 1, b->nxp, ce, 1, p->nxs, X3D_FFT_R2C, batch, &ws[0]));
     X3D_FFT(hipfftMakePlanMany(p->plan_x_bw, 1, nn, ce, 1, p->nxs, re, 1, b->nxp, X3D_FFT_C2R, batch, &ws[1]));
     // z transform on the z-contiguous copy T[ys*nxs][nz]
     X3D_FFT(hipfftMakePlanMany(p->plan_z, 1, nzv, nzv, 1, p->nz, nzv, 1, p->nz, X3D_FFT_C2C, zstride, &ws[2]));
-    size_t wmax = 0;
-    for (int i = 0; i < 3; i++) wmax = ws[i] > wmax ? ws[i] : wmax;
-    if (wmax) X3D_HIP(hipMalloc(&p->work, wmax));
-    for (int i = 0; i < 3; i++) X3D_FFT(hipfftSetWorkArea(*pl[i], p->work));
+    if (int rc = fft_plans_share_work(pl, ws, nullptr, 3, &p->work)) return rc;
     if (int rc = x3d_fft512_init()) return rc;
     *out = p;
     return 0;
@@ -181,8 +120,9 @@ extern "C" int x3d_sfft_destroy(x3d_sfft *p)
 {
     X3D_RANGE(__func__);
     if (!p) return 0;
-    hipfftDestroy(p->plan_x_fw); hipfftDestroy(p->plan_x_bw); hipfftDestroy(p->plan_z);
-    hipFree(p->c0); hipFree(p->t); hipFree(p->waves); hipFree(p->ab); hipFree(p->work);
+    hipfftHandle *pl[3] = {&p->plan_x_fw, &p->plan_x_bw, &p->plan_z};
+    fft_plans_destroy(pl, 3, p->work);
+    hipFree(p->c0); hipFree(p->t); hipFree(p->waves); hipFree(p->ab);
     delete p;
     return 0;
 }
@@ -211,14 +151,7 @@ extern "C" int x3d_sfft_set_waves(x3d_sfft *p, const real_t *waves, const real_t
         for (size_t i = 0; i < n; i++) rw[i] = waves[i] < 1.e-16 ? 0.0 : -1.0 / waves[i];
         X3D_HIP(hipMemcpy(p->waves, rw.data(), sizeof(real_t) * n, hipMemcpyHostToDevice));
     }
-    const real_t *src[6] = {ax, bx, ay, by, az, bz};
-    const int len[6] = {p->nx, p->nx, p->ny, p->ny, p->nz, p->nz};
-    real_t *d = p->ab;
-    for (int i = 0; i < 6; i++) {
-        X3D_HIP(hipMemcpy(d, src[i], sizeof(real_t) * len[i], hipMemcpyHostToDevice));
-        d += len[i];
-    }
-    return 0;
+    return spec_ab_upload(p->ab, p->nx, p->ny, p->nz, p->nx, ax, bx, ay, by, az, bz);
 }
 
 // x R2C, y forward; the result lands in sendbuf as [peer][zl][ys][nxs]
@@ -257,9 +190,7 @@ static int sfft_fft_z_part(x3d_sfft *p, real_t *recvbuf, int dir, int part, bool
     real2_t *R = (real2_t *)recvbuf + (size_t)part * p->nz * W, *T = p->t + (size_t)part * p->nz * W;
     if (dir == 0) {
         ProfScope ps(p->b, X3D_K_PACK);
-        hipLaunchKernelGGL(k_sfft_transpose, dim3((W + 31) / 32, (p->nz + 31) / 32), dim3(256), 0, p->b->stream, T,
-                           (const real2_t *)R, W, p->nz);
-        X3D_HIP(hipGetLastError());
+        if (int rc = transpose32<real2_t>(p->b->stream, T, (const real2_t *)R, W, p->nz)) return rc;
     }
     {
         ProfScope ps(p->b, X3D_K_FFT, 3);
@@ -269,9 +200,7 @@ static int sfft_fft_z_part(x3d_sfft *p, real_t *recvbuf, int dir, int part, bool
     }
     if (dir == 1) {
         ProfScope ps(p->b, X3D_K_PACK);
-        hipLaunchKernelGGL(k_sfft_transpose, dim3((p->nz + 31) / 32, (W + 31) / 32), dim3(256), 0, p->b->stream, R,
-                           (const real2_t *)T, p->nz, W);
-        X3D_HIP(hipGetLastError());
+        if (int rc = transpose32<real2_t>(p->b->stream, R, (const real2_t *)T, p->nz, W)) return rc;
     }
     return 0;
 }
@@ -294,8 +223,6 @@ extern "C" int x3d_sfft_fft_z(x3d_sfft *p, real_t *recvbuf, int dir)
 static int sfft_postprocess_part(x3d_sfft *p, real_t *recvbuf, int part, bool fused_ok)
 {
     X3D_REQUIRE(p && recvbuf && part >= 0 && part < p->parts, "x3d_sfft_postprocess_000_part: bad argument");
-    const real_t *ax = p->ab, *bx = ax + p->nx, *ay = bx + p->nx, *by = ay + p->ny, *az = by + p->ny,
-                 *bz = az + p->nz;
     const size_t off = (size_t)part * p->nz * p->ysc * p->nxs;  // waves[ys][nxs][nz] and T share the part offset
     if (p->fused_z && fused_ok) {
         bool ok = false;
@@ -306,10 +233,11 @@ static int sfft_postprocess_part(x3d_sfft *p, real_t *recvbuf, int part, bool fu
         X3D_REQUIRE(ok, "x3d_sfft_postprocess_000_part: fused z stage refused");
         return 0;
     }
+    const SpecAB t = spec_ab_view(p->ab, p->nx, p->ny, p->nz);
     dim3 grid((p->nz + 255) / 256, p->nxs, p->ysc);
     ProfScope ps(p->b, X3D_K_SPECTRAL);
     hipLaunchKernelGGL(k_process_spectral_000_slab, grid, dim3(256), 0, p->b->stream, p->t + off, p->waves + off, p->nxs,
-                       p->ysc, p->nz, p->rz * p->ys + part * p->ysc, p->nx, p->ny, ax, bx, ay, by, az, bz);
+                       p->ysc, p->nz, p->rz * p->ys + part * p->ysc, p->nx, p->ny, t.ax, t.bx, t.ay, t.by, t.az, t.bz);
     X3D_HIP(hipGetLastError());
     return 0;
 }

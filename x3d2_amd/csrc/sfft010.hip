@@ -24,19 +24,8 @@
 // transforms, the paired split and the pentadiagonal solves run as soon as it has arrived, beside the transfer of the
 // next groups (the *_part entry points; x3d2_amd/poisson_fft.py, HipSlabPoissonFFT010.poisson_010).  T, waves and the
 // factors are stored per group: T[part][ny][xsc][nz], lu[part][5][n][xsc][nz].
-#include <hipfft/hipfft.h>
-
+#include "fft_util.h"
 #include "spectral010.h"
-
-#define X3D_FFT(expr)                                                                          \
-    do {                                                                                       \
-        hipfftResult r_ = (expr);                                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                                            \
-            x3d_set_error("%s failed: hipfft error %d (%s:%d)", #expr, (int)r_, __FILE__,      \
-                          __LINE__);                                                           \
-            return 3;                                                                          \
-        }                                                                                      \
-    } while (0)
 
 struct x3d_sfft010 {
     x3d_backend *b;
@@ -89,34 +78,6 @@ __global__ void __launch_bounds__(256)
     dst[m * part_stride + ((long)j * xsc + i) * nz + k] = src[((long)k * rows + j) * xs + m * xsc + i];
 }
 
-// 32 x 32 tiles through LDS: src [nB][nA] (A contiguous) -> dst [nA][nB] (B contiguous)
-template <class E>
-__global__ void __launch_bounds__(256) k_sfft010_transpose(E *__restrict__ dst, const E *__restrict__ src, long nA, long nB)
-{
-    __shared__ E tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const long a0 = (long)blockIdx.x * 32, b0 = (long)blockIdx.y * 32;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const long bb = b0 + ty + 8 * r, aa = a0 + tx;
-        if (aa < nA && bb < nB) tile[ty + 8 * r][tx] = src[bb * nA + aa];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const long aa = a0 + ty + 8 * r, bb = b0 + tx;
-        if (aa < nA && bb < nB) dst[aa * nB + bb] = tile[tx][ty + 8 * r];
-    }
-}
-template <class E>
-static int transpose_launch(hipStream_t st, E *dst, const E *src, long nA, long nB)
-{
-    hipLaunchKernelGGL(k_sfft010_transpose<E>, dim3((unsigned)((nA + 31) / 32), (unsigned)((nB + 31) / 32)), dim3(256), 0, st,
-                       dst, src, nA, nB);
-    X3D_HIP(hipGetLastError());
-    return 0;
-}
-
 extern "C" int x3d_sfft010_create_parts(x3d_backend *b, x3d_sfft010 **out, const int nglob[3], int pz, int rz, int parts);
 extern "C" int x3d_sfft010_create(x3d_backend *b, x3d_sfft010 **out, const int nglob[3], int pz, int rz)
 {
@@ -162,14 +123,11 @@ extern "C" int x3d_sfft010_create_parts(x3d_backend *b, x3d_sfft010 **out, const
     X3D_HIP(hipMalloc(&p->waves, sizeof(real_t) * nw));
     X3D_HIP(hipMalloc(&p->t, sizeof(real2_t) * nw));
     p->nab_x = p->nx > p->nxs ? p->nx : p->nxs;
-    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * 2 * ((size_t)p->nab_x + p->ny + p->nz)));
-    X3D_HIP(hipMemset(p->ab, 0, sizeof(real_t) * 2 * ((size_t)p->nab_x + p->ny + p->nz)));
+    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * spec_ab_elems(p->nab_x, p->ny, p->nz)));
+    X3D_HIP(hipMemset(p->ab, 0, sizeof(real_t) * spec_ab_elems(p->nab_x, p->ny, p->nz)));
     hipfftHandle *pl[6] = {&p->plan_xy_fw, &p->plan_xy_bw, &p->plan_z, &p->plan_x_fw, &p->plan_x_bw, &p->plan_y};
     size_t ws[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 6; i++) {
-        X3D_FFT(hipfftCreate(pl[i]));
-        X3D_FFT(hipfftSetAutoAllocation(*pl[i], 0));
-    }
+    if (int rc = fft_plans_create(pl, 6)) return rc;
     // real side: the pitched block's planes; spectral side: dense rows of nxs (the first nxm are written)
     int nn[2] = {p->ny, p->nx}, re[2] = {b->nyp, b->nxp}, ce[2] = {p->ny, p->nxs};
     const hipfftResult r_fw = hipfftMakePlanMany(p->plan_xy_fw, 2, nn, re, 1, b->nxp * b->nyp, ce, 1, p->ny * p->nxs,
@@ -192,13 +150,9 @@ extern "C" int x3d_sfft010_create_parts(x3d_backend *b, x3d_sfft010 **out, const
     // z transform on the z-contiguous copy T[ny * xs][nz]
     int nzv[1] = {p->nz}, ze[1] = {p->nz};
     X3D_FFT(hipfftMakePlanMany(p->plan_z, 1, nzv, ze, 1, p->nz, ze, 1, p->nz, X3D_FFT_C2C, p->ny * p->xsc, &ws[2]));
-    size_t wmax = 0;
-    for (int i = 0; i < 6; i++) wmax = ws[i] > wmax ? ws[i] : wmax;
-    if (wmax) X3D_HIP(hipMalloc(&p->work, wmax));
-    for (int i = 0; i < 6; i++) {
-        const bool used = i == 2 || (p->split_xy ? i >= 3 : i < 2);
-        if (used) X3D_FFT(hipfftSetWorkArea(*pl[i], p->work));
-    }
+    bool made[6];  // z always; the 2-D pair or its 1-D replacements
+    for (int i = 0; i < 6; i++) made[i] = i == 2 || (p->split_xy ? i >= 3 : i < 2);
+    if (int rc = fft_plans_share_work(pl, ws, made, 6, &p->work)) return rc;
     *out = p;
     return 0;
 }
@@ -207,9 +161,9 @@ extern "C" int x3d_sfft010_destroy(x3d_sfft010 *p)
 {
     X3D_RANGE(__func__);
     if (!p) return 0;
-    hipfftDestroy(p->plan_xy_fw); hipfftDestroy(p->plan_xy_bw); hipfftDestroy(p->plan_z);
-    hipfftDestroy(p->plan_x_fw); hipfftDestroy(p->plan_x_bw); hipfftDestroy(p->plan_y);
-    hipFree(p->c0); hipFree(p->t); hipFree(p->waves); hipFree(p->ab); hipFree(p->work); hipFree(p->lu[0]); hipFree(p->lu[1]);
+    hipfftHandle *pl[6] = {&p->plan_xy_fw, &p->plan_xy_bw, &p->plan_z, &p->plan_x_fw, &p->plan_x_bw, &p->plan_y};
+    fft_plans_destroy(pl, 6, p->work);
+    hipFree(p->c0); hipFree(p->t); hipFree(p->waves); hipFree(p->ab); hipFree(p->lu[0]); hipFree(p->lu[1]);
     delete p;
     return 0;
 }
@@ -238,15 +192,7 @@ extern "C" int x3d_sfft010_set_waves(x3d_sfft010 *p, const real_t *waves, const 
         X3D_HIP(hipGetLastError());
         X3D_HIP(hipStreamSynchronize(p->b->stream));
     }
-    const real_t *src[6] = {ax, bx, ay, by, az, bz};
-    const int len[6] = {p->nx, p->nx, p->ny, p->ny, p->nz, p->nz};
-    const int slot[6] = {p->nab_x, p->nab_x, p->ny, p->ny, p->nz, p->nz};
-    real_t *d = p->ab;
-    for (int i = 0; i < 6; i++) {
-        X3D_HIP(hipMemcpy(d, src[i], sizeof(real_t) * len[i], hipMemcpyHostToDevice));
-        d += slot[i];
-    }
-    return 0;
+    return spec_ab_upload(p->ab, p->nab_x, p->ny, p->nz, p->nx, ax, bx, ay, by, az, bz);
 }
 
 // a0, a1: this rank's columns of the pentadiagonal operators, [5][nz][n][xs] (pad columns zero); sym: odd / even rows
@@ -340,7 +286,7 @@ extern "C" int x3d_sfft010_fft_z_part(x3d_sfft010 *p, real_t *recvbuf, int dir, 
     real2_t *W = (real2_t *)recvbuf + (size_t)part * p->nz * cols, *T = p->t + (size_t)part * p->nz * cols;
     if (dir == 0) {
         ProfScope ps(p->b, X3D_K_PACK);
-        if (int rc = transpose_launch<real2_t>(p->b->stream, T, (const real2_t *)W, cols, p->nz)) return rc;
+        if (int rc = transpose32<real2_t>(p->b->stream, T, (const real2_t *)W, cols, p->nz)) return rc;
     }
     {
         ProfScope ps(p->b, X3D_K_FFT, 3);
@@ -349,7 +295,7 @@ extern "C" int x3d_sfft010_fft_z_part(x3d_sfft010 *p, real_t *recvbuf, int dir, 
     }
     if (dir == 1) {
         ProfScope ps(p->b, X3D_K_PACK);
-        if (int rc = transpose_launch<real2_t>(p->b->stream, W, (const real2_t *)T, p->nz, cols)) return rc;
+        if (int rc = transpose32<real2_t>(p->b->stream, W, (const real2_t *)T, p->nz, cols)) return rc;
     }
     return 0;
 }
@@ -369,14 +315,13 @@ extern "C" int x3d_sfft010_postprocess_010_part(x3d_sfft010 *p, real_t *recvbuf,
     X3D_RANGE(__func__);
     X3D_REQUIRE(p && recvbuf && part >= 0 && part < p->parts, "x3d_sfft010_postprocess_010_part: bad argument");
     ProfScope ps(p->b, X3D_K_SPECTRAL);
-    const real_t *ax = p->ab, *bx = ax + p->nab_x, *ay = bx + p->nab_x, *by = ay + p->ny, *az = by + p->ny,
-                 *bz = az + p->nz;
+    const SpecAB t = spec_ab_view(p->ab, p->nab_x, p->ny, p->nz);
     const size_t off = (size_t)part * p->nz * p->ny * p->xsc;
     const int n = p->sym ? p->ny / 2 : p->ny;
     real_t *lu[2] = {p->lu[0] ? p->lu[0] + (size_t)part * 5 * n * p->xsc * p->nz : nullptr,
                      p->lu[1] ? p->lu[1] + (size_t)part * 5 * n * p->xsc * p->nz : nullptr};
     return spectral_010_launch_t<true>(p->b->stream, p->t + off, p->waves + off, p->xsc, p->nx, p->ny, p->nz,
-                                       p->rz * p->xs + part * p->xsc, ax, bx, ay, by, az, bz, p->stretched, p->sym, lu);
+                                       p->rz * p->xs + part * p->xsc, t.ax, t.bx, t.ay, t.by, t.az, t.bz, p->stretched, p->sym, lu);
 }
 
 extern "C" int x3d_sfft010_postprocess_010(x3d_sfft010 *p, real_t *recvbuf)

@@ -28,15 +28,12 @@
 // group): the x transforms and the z pair of rows group a run when ITS blocks are in, beside the transfers of the rows
 // groups behind it (poisson_fft.HipSlabPoissonFFTZ._pipelined; 8 emulated ranks 63.2 -> 54.1 ms per step,
 // profiles/r05_yslab_pipeline_timeline.txt).  Same kernels on the same data: bit for bit the unsplit solve.
+#include "fft_util.h"
 #include "zfft_tile.h"
 
 #define SZ_PX 520
 #define SZ_MAXPARTS 8
 
-int x3d_fft512_init();
-const real2_t *x3d_fft512_twiddles();
-int x3d_fft512_peers_yl(x3d_backend *b, real2_t *R, long W, int npeers, const real_t *rw, const real_t *ab, int nx, int ny,
-                        int nz, int xs, int xoff, int kz0, int part);
 int x3d_ztile_fft_run(x3d_backend *b, real_t *f, const ZfArg &zf, bool fwd, int y0, int nyr);
 int x3d_ytile_tds_pair_zf(x3d_backend *b, int mode, real_t *out1, real_t *out2, const real_t *in1, const real_t *in2,
                           const x3d_tdsops *ta, const x3d_tdsops *tb, const ZfArg &zf, bool *done, int y0, int nyr);
@@ -105,7 +102,7 @@ extern "C" int x3d_sfftz_create(x3d_backend *b, x3d_sfftz **out, const int nglob
     X3D_HIP(hipMalloc(&p->c, sizeof(real2_t) * 257 * 512 * SZ_PX));
     X3D_HIP(hipMemset(p->c, 0, sizeof(real2_t) * 257 * 512 * SZ_PX));
     X3D_HIP(hipMalloc(&p->rw, sizeof(real_t) * 257 * p->xs * 512 * py));
-    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * 2 * (512 + 512 * py + 512)));
+    X3D_HIP(hipMalloc(&p->ab, sizeof(real_t) * spec_ab_elems(512, 512 * py, 512)));
     *out = p;
     return 0;
 }
@@ -146,14 +143,7 @@ extern "C" int x3d_sfftz_set_waves(x3d_sfftz *p, const real_t *rw, const real_t 
     X3D_RANGE(__func__);
     X3D_REQUIRE(p && rw && ax && bx && ay && by && az && bz, "null argument");
     X3D_HIP(hipMemcpy(p->rw, rw, sizeof(real_t) * 257 * p->xs * 512 * p->py, hipMemcpyHostToDevice));
-    real_t *d = p->ab;
-    const real_t *src[6] = {ax, bx, ay, by, az, bz};
-    const int len[6] = {512, 512, 512 * p->py, 512 * p->py, 512, 512};
-    for (int i = 0; i < 6; i++) {
-        X3D_HIP(hipMemcpy(d, src[i], sizeof(real_t) * len[i], hipMemcpyHostToDevice));
-        d += len[i];
-    }
-    return 0;
+    return spec_ab_upload(p->ab, 512, 512 * p->py, 512, 512, ax, bx, ay, by, az, bz);
 }
 
 static ZfArg zfarg(const x3d_sfftz *p) { return ZfArg{p->c, x3d_fft512_twiddles(), 512, (long)SZ_PX}; }

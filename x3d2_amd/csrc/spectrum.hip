@@ -6,23 +6,10 @@
 // Deterministic like the other reductions (stats.hip, "profiles"; checkpoint.hip): no floating-point atomics, neither
 // in LDS nor in global memory; every sum is formed in an order that depends on the launch geometry only, and the launch
 // geometry on the dims only.  Bins, partial sums and running means are FP64 in both flavours.
-#include <hipfft/hipfft.h>
-
 #include <cmath>
 
-#include "common.h"
-
+#include "fft_util.h"
 #include "poisson_priv.h"
-
-#define SPEC_FFT(expr)                                                                         \
-    do {                                                                                       \
-        hipfftResult r_ = (expr);                                                              \
-        if (r_ != HIPFFT_SUCCESS) {                                                            \
-            x3d_set_error("%s failed: hipfft error %d (%s:%d)", #expr, (int)r_, __FILE__,      \
-                          __LINE__);                                                           \
-            return 3;                                                                          \
-        }                                                                                      \
-    } while (0)
 
 #define SPEC_MAXBINS 4096
 #define SPEC_MAXGROUPS 2048        // workgroups of the shell launch (8 per CU)
@@ -315,6 +302,7 @@ extern "C" int x3d_spectra_create(x3d_backend *b, x3d_spectra **out, int mode, c
         int nn[2] = {nz, nx};
         int re[2] = {b->nzp, b->nyp * b->nxp}, ce[2] = {nz, ny * s->nxs};
         size_t ws = 0;
+// (not fft_util.h's X3D_FFT on purpose: a failure here frees what has been allocated so far before it returns)
 #define SPEC_TRY_FFT(expr)                                                                     \
     do {                                                                                       \
         hipfftResult r_ = (expr);                                                              \
@@ -415,8 +403,8 @@ extern "C" int x3d_spectra_sample(x3d_spectra *s, x3d_poisson *p, const x3d_real
     }
     {
         ProfScope ps(b, X3D_K_FFT, 1);
-        SPEC_FFT(hipfftSetStream(s->plan, b->stream));
-        SPEC_FFT(x3d_fftExecR2C(s->plan, (x3d_fft_real *)const_cast<x3d_real *>(field), (x3d_fft_cplx *)s->c));
+        X3D_FFT(hipfftSetStream(s->plan, b->stream));
+        X3D_FFT(x3d_fftExecR2C(s->plan, (x3d_fft_real *)const_cast<x3d_real *>(field), (x3d_fft_cplx *)s->c));
     }
     return spectra_reduce(s, s->c, s->nxs, slot);
 }

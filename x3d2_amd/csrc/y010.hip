@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "fft512_core.h"
+#include "fft_util.h"
 #include "spectral010.h"
 
 #define Y010_P 274  // >= 271 (fft256_wave's layouts) and = 2 mod 16: the 8 pencils' rows j sit in different LDS banks
@@ -445,8 +446,6 @@ __global__ void __launch_bounds__(512) k_y010(real2_t *__restrict__ c, const rea
     for (int p = 0; p < 4; p++) base[(size_t)(tr + 64 * p) * g.nxs + tx] = sm[tx * Y010_P + tr + 64 * p];
 }
 
-const real2_t *x3d_fft512_twiddles();
-int x3d_fft512_init();
 
 // c[nz][256][nxs], x and z already transformed (mode 0, 3) / still transformed (mode 1, 4).  tables = ax bx ay by az bz
 // back to back (global lengths nx nx ny ny nz nz).  *done = false: not served (other ny, odd row pitch)

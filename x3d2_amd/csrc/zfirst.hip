@@ -18,16 +18,13 @@
 // rotations cancel pairwise: |b - i a| = 1, so any consistent choice gives the result up to rounding).
 #include <vector>
 
+#include "fft_util.h"
 #include "poisson_priv.h"
 #include "zfft_tile.h"
 
 #define ZH_PX 520  // row pitch of C in complex numbers (512 + 8: consecutive y rows do not share an HBM channel pattern)
 
-int x3d_fft512_init();
-const real2_t *x3d_fft512_twiddles();
 int x3d_ztile_fft_run(x3d_backend *b, real_t *f, const ZfArg &zf, bool fwd, int y0, int nyr);
-int x3d_fft512_run_zh(x3d_backend *b, real2_t *c, long px, int kz0, int nkz, const real_t *rwZ, const real_t *ab, int nx,
-                      int ny, int nz);
 
 // rwZ[kz][x][y] = -1 / waves(min(x, nx - x), y, kz)  (0 where waves < 1e-16); waves = [nz][ny][nxs] (x: nx/2+1 modes)
 __global__ void __launch_bounds__(256)
