@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -40,6 +40,13 @@ ceiling, next to x3d_scalar_product on a field of the same run; (b) a whole thre
 plus three reductions plus the running-mean update; (c) the composed path in the same process, get_spectral plus numpy
 binning for three fields (wall clock: it waits for the host); (d) the plane reduction alone and a three-field plane sample
 at 1024 x 257 x 512.  `step_share` = fraction of the 40 ms of a 512^3 TGV step (README).
+
+Family "diagnostics" (--snap-n^3 = 512^3, median of --stat-iters with the quartiles as spread; not part of "all"): (a) the
+x3d_diag_reduce launches alone (HIP events) in GB/s on the twelve blocks they must read, next to the 6.2 TB/s copy ceiling
+and x3d_scalar_product on the same box; (b) a whole Diagnostics sample -- nine gradients, the reduction, the divergence and
+its max / sum -- as wall clock around a device sync; (c) Monitoring.write_step + kinetic_energy on the same state in the
+same process, the same way, with the host waits of each (x3d_backend_counter 3); (d) a 20-step TGV run with idiagfreq = 1
+against the same run without: added wall time per step.  The lines are appended to profiles/diagnostics.jsonl.
 """
 import argparse
 import json
@@ -517,6 +524,118 @@ def bench_spectra(args):
     row("spectra: three-field plane sample (3 2-D transforms + 3 reductions + mean)", dims, t, tmin, k)
 
 
+def bench_diagnostics(args):
+    """one JSON line per measurement of the "diagnostics" family, printed and appended to profiles/diagnostics.jsonl"""
+    import ctypes
+    import tempfile
+
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.common import DIR_X, DIR_Y, DIR_Z, VERT
+    from x3d2_amd.diagnostics import Diagnostics, DiagnosticsConfig
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    tmp = tempfile.mkdtemp(prefix="x3d_diag_")
+    out_path = os.path.join(ROOT, "profiles", "diagnostics.jsonl")
+
+    def emit(row):
+        row = dict({"family": "diagnostics", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    def spread(times):
+        q1, med, q3 = (float(v) for v in np.percentile(times, [25, 50, 75]))
+        return {"ms_median": med, "ms_q1": q1, "ms_q3": q3, "ms_min": float(min(times)), "samples": len(times)}
+
+    def events(b, fn):
+        ms, times = ctypes.c_float(), []
+        for i in range(args.stat_warmup + args.stat_iters):
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            fn()
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times.append(ms.value)
+        return times
+
+    def wall(b, fn):
+        times = []
+        for i in range(args.stat_warmup + args.stat_iters):
+            b.sync()
+            t0 = time.perf_counter()
+            fn()
+            b.sync()
+            if i >= args.stat_warmup:
+                times.append((time.perf_counter() - t0) * 1e3)
+        return times
+
+    case = make_tgv(n, fused=True)
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    case.step(1)
+    s.flush_grad()
+    dg = Diagnostics(s, DiagnosticsConfig(prefix=os.path.join(tmp, "a")))
+    # (a) the reduction launches alone, on gradients computed once
+    grads = []
+    for f in (s.u, s.v, s.w):
+        for dirps, d in ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z)):
+            g = al.get_block(DIR_X, VERT)
+            b.tds_apply(g, f, dirps.der1st, d)
+            grads.append(g)
+    t = spread(events(b, lambda: dg.reduce(s.u, s.v, s.w, grads)))
+    nbytes = 12 * rb * n ** 3
+    emit(dict({"op": "x3d_diag_reduce: both launches (12 blocks read)", "bytes": nbytes, "GBs": nbytes / t["ms_median"] / 1e6,
+               "ceiling": nbytes / t["ms_median"] / 1e6 / 6200.0, "row_pitch": b.padded_dims[0]}, **t))
+    t = spread(events(b, lambda: b.scalar_product(s.u, s.v)))
+    nbytes = 2 * rb * n ** 3
+    emit(dict({"op": "x3d_scalar_product (k_reduce) on the same box", "bytes": nbytes, "GBs": nbytes / t["ms_median"] / 1e6,
+               "ceiling": nbytes / t["ms_median"] / 1e6 / 6200.0}, **t))
+    for g in grads:
+        al.release_block(g)
+    # (b) a whole sample, (c) the monitoring row it replaces: wall clock around a device sync, same state, same process
+    count = [0]
+
+    def sample():
+        count[0] += 1
+        dg.sample(count[0])
+        dg.poll()
+
+    s0 = b.sync_count()
+    t = spread(wall(b, sample))
+    emit(dict({"op": "Diagnostics sample: 9 gradients + reduction + divergence + max / sum (wall clock)",
+               "stream_syncs_per_call": (b.sync_count() - s0) / float(args.stat_warmup + args.stat_iters)}, **t))
+    dg.finalise()
+
+    def monitoring():
+        case.monitoring.write_step(0.0, s.u, s.v, s.w)
+        case.monitoring.kinetic_energy()
+
+    s0 = b.sync_count()
+    t2 = spread(wall(b, monitoring))
+    emit(dict({"op": "Monitoring.write_step + kinetic_energy (wall clock)",
+               "stream_syncs_per_call": (b.sync_count() - s0) / float(args.stat_warmup + args.stat_iters)}, **t2))
+    emit({"op": "gate: sample faster than monitoring", "sample_ms_median": t["ms_median"], "monitoring_ms_median": t2["ms_median"],
+          "passed": bool(t["ms_median"] < t2["ms_median"])})
+    del case, s, b, al, dg, grads
+    torch.cuda.empty_cache()
+    # (d) a 20-step run with a row per step against the same run without
+    res = {}
+    for with_diag in (False, True):
+        case = make_tgv(n, fused=True)
+        if with_diag:
+            case.diagnostics = Diagnostics(case.solver, DiagnosticsConfig(prefix=os.path.join(tmp, "d")))
+        case.run(n_iters=3)
+        case.solver.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        case.solver.backend.sync()
+        res[with_diag] = (time.perf_counter() - t0) * 1e3
+        del case
+        torch.cuda.empty_cache()
+    emit({"op": "TGV, fused, RK3: 20 steps, idiagfreq 1", "wall_ms_without": res[False], "wall_ms_with": res[True],
+          "added_ms_per_step": (res[True] - res[False]) / 20.0})
+
+
 def sample_of(sp):
     count = [sp.sample_count]
 
@@ -532,7 +651,7 @@ def main():
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra"))
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -547,7 +666,9 @@ def main():
         bench_checkpoint(args)
     if args.family == "spectra":
         bench_spectra(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra"):
+    if args.family == "diagnostics":
+        bench_diagnostics(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics"):
         return
     import torch
     from x3d2_amd import Mesh

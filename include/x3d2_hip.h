@@ -856,6 +856,30 @@ int x3d_spectra_read(x3d_spectra *s, int which, double *host);
 /* the running means <- host[nslots][values per slot] (restart) */
 int x3d_spectra_load(x3d_spectra *s, const double *host_mean);
 
+/* ---- diagnostics series on the device (csrc/diagnostics.hip): every scalar of a monitoring row (src/postprocess/
+ * monitoring.f90 writes enstrophy and max / mean |div u|; kinetic energy, dissipation, wall shear, maxima and CFL are this
+ * project's additions) from one pass over u, v, w and the nine velocity gradients.  A row is 16 doubles in BOTH flavours:
+ *    0..2  sum u^2, v^2, w^2        3  sum [(wy-vz)^2 + (uz-wx)^2 + (vx-uy)^2]
+ *    4     sum [ux^2 + vy^2 + wz^2 + 1/2 ((uy+vx)^2 + (uz+wx)^2 + (vz+wy)^2)]   (= sum S_ij S_ij)
+ *    5, 6  sum over (x, z) of uy on the first / the last y row; 0 where first_y / last_y is 0
+ *    7     sum |f|  (x3d_diag_max_sum)          8..10  max |u|, |v|, |w|          11  max of slot 3's integrand
+ *    12    max (|u| ih_x[i] + |v| ih_y[j] + |w| ih_z[k])          13  max |f|  (x3d_diag_max_sum)          14, 15  0
+ * all over the dims interior of the blocks (row padding is never read into a result).  Two stages, deterministic: per-workgroup
+ * partials in a fixed order in the backend's reduction buffer, added in index order by a second small launch; no
+ * floating-point atomics; the launch geometry depends on dims alone.  Both calls are ordered on the backend's stream, never
+ * wait for the host, and run a queue of the deferred-execution layer first.  A bad argument is an error and launches nothing. */
+typedef struct x3d_diag_params {
+    const double *ih_x, *ih_y, *ih_z; /* device tables of inverse spacings, dims[0], dims[1], dims[2] values */
+    int first_y, last_y;              /* this rank owns the first / the last GLOBAL y row */
+} x3d_diag_params;
+/* grads: dudx, dudy, dudz, dvdx, dvdy, dvdz, dwdx, dwdy, dwdz (x3d_compute_vorticity's order), VERT blocks like u, v, w.
+ * Writes every slot of row_dev except 7 and 13. */
+int x3d_diag_reduce(x3d_backend *b, const x3d_real *u, const x3d_real *v, const x3d_real *w, const x3d_real *const grads[9],
+                    const int dims[3], const x3d_diag_params *params, double *row_dev);
+/* x3d_field_max_sum's reduction with its final stage on the device (the same partials added in the same order: the same bits):
+ * row_dev[13] = max |f|, row_dev[7] = sum |f| */
+int x3d_diag_max_sum(x3d_backend *b, const x3d_real *f, const int dims[3], double *row_dev);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -257,6 +257,8 @@ PROTOTYPES = {
     "x3d_spectra_accumulate": (I, [VP, ctypes.c_long]),
     "x3d_spectra_read": (I, [VP, I, ctypes.POINTER(ctypes.c_double)]),
     "x3d_spectra_load": (I, [VP, ctypes.POINTER(ctypes.c_double)]),
+    "x3d_diag_reduce": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), c_int_p, VP, VP]),
+    "x3d_diag_max_sum": (I, [VP, VP, c_int_p, VP]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),
@@ -270,6 +272,11 @@ PROTOTYPES = {
 class SnapshotVar(ctypes.Structure):
     """x3d_snapshot_var of include/x3d2_hip.h"""
     _fields_ = [("kind", I), ("scale", REAL), ("src", VP * 9)]
+
+
+class DiagParams(ctypes.Structure):
+    """x3d_diag_params of include/x3d2_hip.h"""
+    _fields_ = [("ih_x", VP), ("ih_y", VP), ("ih_z", VP), ("first_y", I), ("last_y", I)]
 
 
 _lib = None

@@ -1122,6 +1122,33 @@ class HipBackend:
         """block until it has (counted by sync_count)"""
         _lib.check(self.lib.x3d_snapshot_wait(self.h, int(handle)))
 
+    # ------------------------------------------------------------ diagnostics series (csrc/diagnostics.hip)
+    def diag_reduce(self, u, v, w, grads, ih, first_y, last_y, row_ptr):
+        """one row of the diagnostics series (16 doubles at the device address row_ptr, slots 7 and 13 untouched) from u,
+        v, w and the nine gradient fields (compute_vorticity's order) in one pass; ih = three device float64 tensors of
+        inverse spacings, one value per local vertex of x, y, z.  No host synchronisation."""
+        if len(grads) != 9:
+            raise X3dError("diag_reduce: nine gradient fields expected")
+        self._need_vert("diag_reduce", u, v, w, *grads)
+        dims = self.mesh.get_dims(VERT)
+        for t, n in zip(ih, dims):
+            if t.dtype != torch.float64 or not t.is_cuda or t.numel() < int(n):
+                raise X3dError("diag_reduce: a spacing table is a device float64 tensor with one value per vertex")
+        prm = _lib.DiagParams(ih[0].data_ptr(), ih[1].data_ptr(), ih[2].data_ptr(), int(bool(first_y)), int(bool(last_y)))
+        p = (VP * 9)(*[g.ptr for g in grads])
+        self.red_epoch += 1  # (the partials live in the reduction buffer)
+        _lib.check(self.lib.x3d_diag_reduce(self.h, u.ptr, v.ptr, w.ptr, p, _lib.ints(*dims), ctypes.byref(prm),
+                                            VP(int(row_ptr))))
+
+    def diag_max_sum(self, f, row_ptr, enforced_data_loc=None):
+        """field_max_mean's reduction with its last stage on the device: max |f| -> slot 13 and sum |f| -> slot 7 of the
+        row at the device address row_ptr.  No host synchronisation."""
+        if f.data_loc == NULL_LOC and enforced_data_loc is None:
+            raise X3dError("The input field to diag_max_sum does not have a valid f%data_loc.")
+        loc = f.data_loc if enforced_data_loc is None else enforced_data_loc
+        self.red_epoch += 1
+        _lib.check(self.lib.x3d_diag_max_sum(self.h, f.ptr, self._dims(loc), VP(int(row_ptr))))
+
     # ------------------------------------------------------------ checkpoints (csrc/checkpoint.hip)
     CKPT_MAXBLOCK = 64  # X3D_CKPT_MAXBLOCK of include/x3d2_hip.h
 

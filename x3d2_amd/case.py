@@ -54,6 +54,8 @@ class BaseCase:
         # optional checkpoint.Checkpoints(solver, cfg, case): run() then writes it (handle_io_step); restarted is set by
         # checkpoint.restore (io_mgr%is_restart, :212)
         self.checkpoints = None
+        # optional diagnostics.Diagnostics(solver, cfg, append=self.restarted): run() then samples, polls and finalises it
+        self.diagnostics = None
         self.restarted = False
         self.step_times = []
         self.initial_conditions()
@@ -186,6 +188,10 @@ class BaseCase:
             # ... a spectra sample too
             if self.spectra is not None and self.spectra.cfg.sample_due(it):
                 sample_due = True
+            # ... and a row of the diagnostics series
+            diag = self.diagnostics
+            if diag is not None and diag.cfg.sample_due(it):
+                sample_due = True
             # ... and so does a snapshot (snapshot_manager.f90:125-126)
             snap = self.snapshots
             snap_due = snap is not None and snap.cfg.due(it)
@@ -200,6 +206,8 @@ class BaseCase:
                 self.stats.update(it)  # update_stats, base_case.f90:319
             if self.spectra is not None:
                 self.spectra.update(it)  # the transforms and the reductions; no host wait
+            if diag is not None:
+                diag.update(it)  # nine gradients, one reduction into the device table; no host wait
             if s.n_output > 0 and it % s.n_output == 0:
                 row = self.postprocess(it, it * s.dt)
                 if verbose and s.mesh.is_root():
@@ -212,7 +220,11 @@ class BaseCase:
             if snap is not None:
                 snap.write(it)  # packs and starts the copy; no host wait
                 snap.poll()     # files of the snapshots whose copies have landed
+            if diag is not None:
+                diag.poll()     # rows of the tables whose copies have landed
             if ckpt is not None:
+                if diag is not None and ckpt.cfg.due(it):
+                    diag.flush()  # the series on disk reaches the checkpoint it may be continued from
                 ckpt.write(it)  # one pack launch, one asynchronous copy; no host wait
                 ckpt.poll()     # the file of a checkpoint whose copy has landed
             s.backend.sync()
@@ -222,6 +234,8 @@ class BaseCase:
             self.snapshots.finalise()
         if self.checkpoints is not None:
             self.checkpoints.finalise()
+        if self.diagnostics is not None:
+            self.diagnostics.finalise()
         return self.monitoring.rows
 
 

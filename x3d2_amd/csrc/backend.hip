@@ -730,6 +730,23 @@ static int run_reduce(x3d_backend *b, const real_t *x, const real_t *y, const in
     return 0;
 }
 
+// stage 1 of run_reduce<RED_ABS> alone (diagnostics.hip finishes on the device): *nparts partial sums at red_buf, as many
+// partial maxima at red_buf + red_cap
+int x3d_reduce_abs_partials_c(x3d_backend *b, const real_t *f, const int dims[3], int *nparts)
+{
+    X3D_REQUIRE(dims[0] > 0 && dims[0] <= b->nxp && dims[1] > 0 && dims[1] <= b->nyp && dims[2] > 0 &&
+                    dims[2] <= b->nzp,
+                "reduction: dims (%d,%d,%d) outside the block", dims[0], dims[1], dims[2]);
+    const long nrow = (long)dims[1] * dims[2];
+    const int grid = (int)(nrow < 2048 ? nrow : 2048);
+    X3D_REQUIRE(grid <= b->red_cap, "reduction: %d partials, the reduction buffer holds %d", grid, b->red_cap);
+    hipLaunchKernelGGL(k_reduce<RED_ABS>, dim3(grid), dim3(256), 0, b->stream, f, f, dims[0], dims[1], dims[2],
+                       (long)b->nxp, (long)b->nyp, b->red_buf, b->red_buf + b->red_cap);
+    X3D_HIP(hipGetLastError());
+    *nparts = grid;
+    return 0;
+}
+
 extern "C" int x3d_scalar_product(x3d_backend *b, const real_t *x, const real_t *y, const int dims[3],
                                   real_t *out)
 {

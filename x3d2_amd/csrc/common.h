@@ -179,6 +179,9 @@ void x3d_snapshot_destroy_c(x3d_backend *b);
 // the backend's stream waits (on the device) for a copy out of the packed buffer `dev` that x3d_snapshot_copy_async started
 // and that may still be in flight; nothing to do if there is none (snapshot.hip; checkpoint.hip packs into such buffers too)
 int x3d_snapshot_wait_for_copy_c(x3d_backend *b, const void *dev);
+// stage 1 of x3d_field_max_sum alone: partial sums of |f| at red_buf, partial maxima at red_buf + red_cap, *nparts of each
+// (at most 2048); no copy, no host wait (backend.hip; diagnostics.hip adds them up on the device)
+int x3d_reduce_abs_partials_c(x3d_backend *b, const real_t *f, const int dims[3], int *nparts);
 #define X3D_BC_PARTS 1024
 // the RK / AB stage of one variable as the epilogue of a tile kernel (xscan.hip, k_ytile_transeq<EPI> / k_ytile_transeq3<EPI>):
 // d = x[ipend] + component;  [store: x[ipend] = d;]  y = base + sum_k c[k] (k == ipend ? d : x[k])

@@ -466,16 +466,23 @@ class Comm:
         dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX, group=self.group)
         return float(t.item())
 
-    def allreduce_tensor(self, t):
-        """sum of a small device tensor over all ranks, in place (the plane sums of the statistics' profile mode);
-        host-staged transport: through host memory"""
+    def allreduce_tensor(self, t, op="sum"):
+        """sum (op="max": maximum) of a small tensor over all ranks, in place (the plane sums of the statistics' profile
+        mode, the landed tables of the diagnostics series); host-staged transport: through host memory; a host tensor
+        over RCCL: through device memory"""
         if self.size == 1:
             return t
+        rop = dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX
         if self.backend == "nccl":
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            if t.is_cuda:
+                dist.all_reduce(t, op=rop, group=self.group)
+            else:
+                d = t.cuda()
+                dist.all_reduce(d, op=rop, group=self.group)
+                t.copy_(d)
             return t
         h = t.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+        dist.all_reduce(h, op=rop, group=self.group)
         t.copy_(h)
         return t
 
