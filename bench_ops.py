@@ -250,17 +250,8 @@ def bench_snapshot(args):
     s.flush_grad()
     nxp = b.padded_dims[0]
 
-    def grads():
-        g = []
-        for f in (s.u, s.v, s.w):
-            for dirps, d in ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z)):
-                o = al.get_block(DIR_X, VERT)
-                b.tds_apply(o, f, dirps.der1st, d)
-                g.append(o)
-        return g
-
     # (a) the pack kernel alone
-    g = grads()
+    g = s.velocity_gradients()
     pv = al.get_block(DIR_X, VERT)
     b.tds_apply(pv, s.pressure, s.zdirps.interpl_p2v, DIR_Z)
     variables = [("copy", s.u, 1.0), ("copy", s.v, 1.0), ("copy", s.w, 1.0), ("copy", pv, 1.0 / s.dt), ("vort", g), ("qcrit", g)]
@@ -294,7 +285,7 @@ def bench_snapshot(args):
                                        snapshot_sp=True, output_fields=fields))
 
     def composed():
-        gg = grads()
+        gg = s.velocity_gradients()
         o = al.get_block(DIR_X, VERT)
         res = []
         for fn in (b.compute_vorticity, b.compute_qcriterion):
@@ -326,7 +317,8 @@ def bench_snapshot(args):
             if i >= 3:
                 walls.append(w)
         print(json.dumps({"family": "snapshot", "op": name, "n": n, "stride": stride, "out_bytes": 4,
-                          "wall_ms_median": float(np.median(walls)), "wall_ms_min": float(min(walls)), "calls": len(walls),
+                          "wall_ms_median": float(np.median(walls)), "wall_ms_q1": float(np.percentile(walls, 25)),
+                          "wall_ms_q3": float(np.percentile(walls, 75)), "wall_ms_min": float(min(walls)), "calls": len(walls),
                           "stream_syncs": b.sync_count() - s0}), flush=True)
     del snap, case, s, b, al
     torch.cuda.empty_cache()
@@ -393,7 +385,8 @@ def bench_checkpoint(args):
 
     # (b) host-visible cost of Checkpoints.write against the only route there was: get_field_data of the same blocks
     ck = Checkpoints(s, CheckpointConfig(checkpoint_freq=1, checkpoint_prefix=os.path.join(tmp, "b")), case)
-    for name, fn, after in (("Checkpoints.write, call to return", lambda it: ck.write(it), lambda: ck.pending and b.snapshot_wait(ck.pending[1])),
+    ck.ring.on_land = lambda payload, raw: None  # (the copies are waited for, no file is written here)
+    for name, fn, after in (("Checkpoints.write, call to return", lambda it: ck.write(it), ck.ring.drain),
                             ("composed: 12 get_field_data", lambda it: [b.get_field_data(f, VERT) for f in state], None)):
         walls, s0 = [], b.sync_count()
         for i in range(2 + 5):
@@ -402,11 +395,11 @@ def bench_checkpoint(args):
             fn(i + 1)
             w = (time.perf_counter() - t0) * 1e3
             if after is not None:
-                after()  # (outside the timed region: the copy has landed; no file is written here)
-                ck.pending = None
+                after()  # (outside the timed region: the copy has landed)
             if i >= 2:
                 walls.append(w)
         print(json.dumps({"family": "checkpoint", "op": name, "n": n, "blocks": 12, "wall_ms_median": float(np.median(walls)),
+                          "wall_ms_q1": float(np.percentile(walls, 25)), "wall_ms_q3": float(np.percentile(walls, 75)),
                           "wall_ms_min": float(min(walls)), "calls": len(walls), "stream_syncs": b.sync_count() - s0}), flush=True)
     del ck, case, s, b, al, state
     torch.cuda.empty_cache()
@@ -418,16 +411,16 @@ def bench_checkpoint(args):
         if with_ckpt:
             ck = Checkpoints(case.solver, CheckpointConfig(checkpoint_freq=5, checkpoint_prefix=os.path.join(tmp, "c"),
                                                            keep_checkpoint=False), case)
-            inner = ck._write_file
+            inner = ck.ring.on_land
 
-            def timed_write():
+            def timed_write(payload, raw):
                 nonlocal in_poll
                 t1 = time.perf_counter()
-                out = inner()
+                out = inner(payload, raw)
                 in_poll += (time.perf_counter() - t1) * 1e3
                 return out
 
-            ck._write_file = timed_write
+            ck.ring.on_land = timed_write
             case.checkpoints = ck
         case.run(n_iters=3)
         case.solver.backend.sync()
@@ -531,7 +524,6 @@ def bench_diagnostics(args):
 
     import torch
     from x3d2_amd import _lib, make_tgv
-    from x3d2_amd.common import DIR_X, DIR_Y, DIR_Z, VERT
     from x3d2_amd.diagnostics import Diagnostics, DiagnosticsConfig
     n, rb = args.snap_n, 4 if _lib.SINGLE else 8
     tmp = tempfile.mkdtemp(prefix="x3d_diag_")
@@ -576,12 +568,7 @@ def bench_diagnostics(args):
     s.flush_grad()
     dg = Diagnostics(s, DiagnosticsConfig(prefix=os.path.join(tmp, "a")))
     # (a) the reduction launches alone, on gradients computed once
-    grads = []
-    for f in (s.u, s.v, s.w):
-        for dirps, d in ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z)):
-            g = al.get_block(DIR_X, VERT)
-            b.tds_apply(g, f, dirps.der1st, d)
-            grads.append(g)
+    grads = s.velocity_gradients()
     t = spread(events(b, lambda: dg.reduce(s.u, s.v, s.w, grads)))
     nbytes = 12 * rb * n ** 3
     emit(dict({"op": "x3d_diag_reduce: both launches (12 blocks read)", "bytes": nbytes, "GBs": nbytes / t["ms_median"] / 1e6,

@@ -74,7 +74,7 @@ def make(tmp_path, keep=True, **kw):
 
 def test_write_poll_and_the_file(tmp_path):
     s, case, ck = make(tmp_path, time_intg="AB3", n_species=1)
-    assert not ck.write(2) and ck._dev is None  # idle: no buffer
+    assert not ck.write(2) and ck.ring.allocated == 0  # idle: no buffer
     s.backend.landed = False
     assert ck.write(3) and s.flushes == 1 and ck.poll() == [] and ck.files == []
     s.backend.landed = True

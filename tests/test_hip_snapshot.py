@@ -142,6 +142,29 @@ def test_pack_copy_is_bit_equal_to_the_numpy_slice(dims, ybc, strides):
     assert n == 15 * len(strides) * len(FIRSTS)
 
 
+def test_copy_ring_of_two_slots_waits_at_the_third_acquire():
+    """CopyRing(b, 2) with 4 KiB slots on a fresh backend: three buffers of distinct bytes submitted without a poll in
+    between.  The host waits once, at the third acquire; the callbacks run in submission order, each on its own bytes."""
+    import torch
+    from x3d2_amd.copyring import CopyRing
+    b = make_backend((17, 6, 5))
+    seen = []
+    ring = CopyRing(b, 2, lambda k, raw: seen.append((k, raw.tobytes())) or k)
+    patterns = [bytes((85 * k + 3 * i + 1) % 256 for i in range(4096)) for k in range(3)]
+    assert ring.allocated == 0 and len(set(patterns)) == 3
+    start = b.sync_count()
+    for k, p in enumerate(patterns):
+        n0 = b.sync_count()
+        slot = ring.acquire(4096)
+        assert b.sync_count() - n0 == (1 if k == 2 else 0), k
+        slot.dev.copy_(torch.frombuffer(bytearray(p), dtype=torch.uint8))
+        ring.submit(slot, 4096, k)
+    assert b.sync_count() - start == 1 and ring.waits == 1 and ring.allocated == 2
+    assert seen == [(0, patterns[0])] and [k for _, k in ring.pending()] == [1, 2]
+    assert ring.drain() == [1, 2] and ring.pending() == []
+    assert seen == list(enumerate(patterns))
+
+
 # ---------------------------------------------------------------- 2. pack, VORT and QCRIT
 @pytest.mark.parametrize("dims,ybc,strides", SHAPES)
 def test_pack_vorticity_and_qcriterion_within_the_rounding_bounds(dims, ybc, strides):

@@ -1161,8 +1161,9 @@ class HipBackend:
         return data, off, off + int(nblock) * 24
 
     def checkpoint_buffers(self, nbytes):
-        """(device staging buffer, pinned host buffer) of nbytes each"""
-        return (torch.empty(int(nbytes), dtype=torch.uint8, device=self.device),
+        """(device staging buffer, pinned host buffer) of nbytes each: what copyring.CopyRing's slots and `restore` are
+        made of.  The device buffer is zero-filled: the diagnostics rows count on the slots nothing writes being 0."""
+        return (torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device),
                 torch.empty(int(nbytes), dtype=torch.uint8, pin_memory=True))
 
     def _block_table(self, fields, who):

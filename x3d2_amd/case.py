@@ -182,25 +182,13 @@ class BaseCase:
         start = s.current_iter + 1
         for it in range(start, n_iters + 1):
             t0 = time.perf_counter()
-            output_due = s.n_output > 0 and it % s.n_output == 0
-            # a statistics sample reads the velocity like an output step does
-            sample_due = self.stats is not None and self.stats.cfg.sample_due(it)
-            # ... a spectra sample too
-            if self.spectra is not None and self.spectra.cfg.sample_due(it):
-                sample_due = True
-            # ... and a row of the diagnostics series
-            diag = self.diagnostics
-            if diag is not None and diag.cfg.sample_due(it):
-                sample_due = True
-            # ... and so does a snapshot (snapshot_manager.f90:125-126)
-            snap = self.snapshots
-            snap_due = snap is not None and snap.cfg.due(it)
-            # ... and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step)
-            ckpt = self.checkpoints
-            if ckpt is not None and ckpt.cfg.due(it):
-                output_due = True
-            self.step(it, more=(it < n_iters and not output_due and not sample_due and not snap_due),
-                      want_pressure=snap_due and s.keep_pressure)
+            diag, snap, ckpt = self.diagnostics, self.snapshots, self.checkpoints
+            # a statistics or spectra sample, a row of the diagnostics series, a snapshot (snapshot_manager.f90:125-126)
+            # and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step) read the velocity like an output step does
+            attached = [a for a in (self.stats, self.spectra, diag, snap, ckpt) if a is not None]
+            read = (s.n_output > 0 and it % s.n_output == 0) or any(a.reads_state(it) for a in attached)
+            snap_due = snap is not None and snap.reads_state(it)
+            self.step(it, more=(it < n_iters and not read), want_pressure=snap_due and s.keep_pressure)
             s.current_iter = it
             if self.stats is not None:
                 self.stats.update(it)  # update_stats, base_case.f90:319

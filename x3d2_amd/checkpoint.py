@@ -7,7 +7,8 @@ blocking copy each.  Here `write` completes a pending velocity correction, launc
 the state into a dense device buffer and forms three integers per block on the way (HipBackend.checkpoint_pack,
 csrc/checkpoint.hip), and starts ONE asynchronous copy of buffer and table into pinned host memory on the copy stream of
 the snapshots.  `write` returns without a host wait; `poll` writes the file once the copy has landed, `finalise` waits
-for it.  One device and one host buffer: a checkpoint that arrives before the previous one has been written waits.
+for it.  The buffers are a ring of 1 slot (copyring.CopyRing): the 2nd acquire waits, that is, a checkpoint that arrives
+before the previous one has been written waits for it.
 
 The state, in this order: u, v, w; phi_<n> per species; for Adams-Bashforth of order > 1 `<name>_rhs_old<j>` for every
 variable in the integrator's list order (after its rotations); with active 3-D statistics their accumulators under
@@ -39,6 +40,7 @@ import numpy as np
 
 from . import _lib
 from .common import VERT, X3dError
+from .copyring import CopyRing
 
 REAL_BYTES = np.dtype(_lib.NP_REAL).itemsize
 
@@ -100,10 +102,9 @@ class Checkpoints:
 
     def __init__(self, solver, cfg, case=None):
         self.solver, self.cfg, self.case = solver, cfg, case
-        self._dev = self._host = None  # made by the first due write: an attached but idle Checkpoints takes nothing
-        self.pending = None            # (iteration, copy handle, names, scalars, dims) while a copy is unwritten
-        self.files = []                # names of the files written so far, .nonfinite ones included
-        self.last_good = None          # the newest finite checkpoint on disk
+        self.ring = CopyRing(solver.backend, 1, self._write_file)  # (an attached but idle Checkpoints takes nothing)
+        self.files = []        # names of the files written so far, .nonfinite ones included
+        self.last_good = None  # the newest finite checkpoint on disk
 
     @property
     def stats(self):
@@ -145,10 +146,14 @@ class Checkpoints:
                 out["case_" + k] = np.asarray(v)
         return out
 
+    def reads_state(self, it):
+        """does write(it) read the solver's fields?  (BaseCase.run then completes the step first)"""
+        return self.cfg.due(it)
+
     def write(self, it):
         """if iteration `it` is due: flush_grad, one pack launch, one asynchronous copy; returns whether a checkpoint
         was taken.  No host wait unless the previous checkpoint is still unwritten."""
-        if not self.cfg.due(it):
+        if not self.reads_state(it):
             return False
         s = self.solver
         b = s.backend
@@ -159,30 +164,25 @@ class Checkpoints:
                            % (len(fields), b.CKPT_MAXBLOCK))
         dims = tuple(int(n) for n in s.mesh.get_dims(VERT))
         _, _, total = b.checkpoint_layout(len(fields), int(np.prod(dims)))
-        if self.pending is not None:  # the second checkpoint before the first was written
-            b.snapshot_wait(self.pending[1])
-            self._write_file()
-        if self._dev is None or self._dev.numel() < total:
-            self._dev, self._host = b.checkpoint_buffers(total)
+        slot = self.ring.acquire(total)  # (the second checkpoint before the first was written waits here)
         scalars = self.scalars(it)  # (now: the file is written later, the run goes on in between)
-        n = b.checkpoint_pack([f for _, f in fields], dims, self._dev)
-        self.pending = (int(it), b.snapshot_copy_async(self._host, self._dev, n), [k for k, _ in fields], scalars, dims)
+        n = b.checkpoint_pack([f for _, f in fields], dims, slot.dev)
+        self.ring.submit(slot, n, (int(it), [k for k, _ in fields], scalars, dims))
         return True
 
     # ------------------------------------------------------------ writing
-    def _write_file(self):
-        it, _, names, scalars, dims = self.pending
+    def _write_file(self, payload, raw):
+        """the ring's landing: the file of what write() packed, from the landed bytes"""
+        it, names, scalars, dims = payload
         b = self.solver.backend
         n = int(np.prod(dims))
         data, off, total = b.checkpoint_layout(len(names), n)
-        raw = self._host.numpy()
         arrays = raw[:data].view(_lib.NP_REAL).reshape(len(names), dims[2], dims[1], dims[0])
         table = raw[off:total].view(np.uint64).reshape(len(names), 3)
         payload = {name: arrays[k] for k, name in enumerate(names)}
         payload.update(scalars)
         payload["names"] = np.array(names)
         payload["checksums"] = table.copy()
-        self.pending = None
         return self.save(it, payload, bool(np.any(table[:, 2] > 0)))
 
     def save(self, it, payload, nonfinite):
@@ -203,16 +203,11 @@ class Checkpoints:
 
     def poll(self):
         """write the checkpoint whose copy has landed; never blocks.  Returns the files written."""
-        if self.pending is not None and self.solver.backend.snapshot_done(self.pending[1]):
-            return [self._write_file()]
-        return []
+        return self.ring.poll()
 
     def finalise(self):
         """wait for and write what is left"""
-        if self.pending is None:
-            return []
-        self.solver.backend.snapshot_wait(self.pending[1])
-        return [self._write_file()]
+        return self.ring.drain()
 
 
 # ---------------------------------------------------------------- restart

@@ -22,5 +22,11 @@ def get_rdr_from_dirs(dir_from, dir_to):
     return 0 if dir_from == dir_to else 10 * dir_from + dir_to
 
 
+def sample_due(it, init, freq):
+    """the sampling rule of the statistics (src/io/stats.f90:83, 129-131), shared by the spectra and the diagnostics
+    series: from iteration `init` on, every `freq` iterations; init <= 0: never"""
+    return init > 0 and it >= init and (it - init) % freq == 0
+
+
 class X3dError(RuntimeError):
     """the reference `error stop`s; the mirror raises"""

@@ -8,10 +8,10 @@ leaves the row's sixteen doubles in a device table (HipBackend.diag_reduce), and
 the max / sum of its block (HipBackend.diag_max_sum).  No call of a sample waits for the host.  A sample holds nine
 transient pool blocks (about 9.3 GiB at 512^3 in FP64); their release is stream-ordered.
 
-Tables.  Row r of the current batch goes to table[r] of one of two device tables of flush_every x 16 doubles.  A full
-table -- and flush() / finalise() -- starts one asynchronous copy into one of two pinned buffers; poll(), once per step,
-turns the tables that have landed into rows and lines of the file.  A table that is needed again before its copy has
-landed waits for it and counts sync_count.  Several ranks: every rank's table holds its local sums and maxima; a landed
+Tables.  Row r of the current batch goes to table[r] of a device table of flush_every x 16 doubles.  A full table -- and
+flush() / finalise() -- starts one asynchronous copy into its pinned twin; poll(), once per step, turns the tables that
+have landed into rows and lines of the file.  The tables are a ring of 2 slots (copyring.CopyRing): the 3rd acquire waits,
+that is, a table that is needed again before it has been landed waits for its copy and counts sync_count.  Several ranks: every rank's table holds its local sums and maxima; a landed
 table is combined in two collectives (sum over slots 0-7, max over slots 8-13).  So that the collectives match, every rank
 flushes at the same sample counts and a table is landed by the second poll() after its flush (waiting for the copy if it
 has to), not whenever its own copy happens to be done.
@@ -36,7 +36,8 @@ import os
 import numpy as np
 import torch
 
-from .common import DIR_X, DIR_Y, DIR_Z, CELL, VERT, BC_NAMES, X3dError
+from .common import DIR_Z, CELL, VERT, BC_NAMES, X3dError, sample_due
+from .copyring import CopyRing
 
 NSLOT = 16
 SUM_SLOTS, MAX_SLOTS = slice(0, 8), slice(8, 14)
@@ -62,13 +63,7 @@ class DiagnosticsConfig:
         return self.initdiag > 0
 
     def sample_due(self, it):
-        if not self.active:
-            return False
-        if it < self.initdiag:
-            return False
-        if (it - self.initdiag) % self.idiagfreq != 0:
-            return False
-        return True
+        return sample_due(it, self.initdiag, self.idiagfreq)
 
 
 # ---------------------------------------------------------------- host side: columns, spacings, file
@@ -197,15 +192,12 @@ class Diagnostics:
         self.last_y = self.y_walls and int(m.nrank_dir[1]) == int(m.nproc_dir[1]) - 1
         self.ih_host = spacing_tables(m)
         self.ih = [torch.from_numpy(a).to(b.device) for a in self.ih_host]
-        self.sync_count = 0
         self.sample_count = 0
-        self._tab = self._host = None  # made by the first sample: an attached but idle Diagnostics takes nothing
+        self.ring = CopyRing(b, 2, self._land)  # (an attached but idle Diagnostics takes nothing)
+        self._slot = None     # the ring slot of the current table, acquired by the first row of a batch
         self._scratch = None
         self._meta = np.zeros((cfg.flush_every, 2), dtype=np.float64)  # (iteration, time) of the current table's rows
         self._count = 0       # rows in the current table
-        self._cur = 0
-        self._pending = [None, None]  # per table: [sequence number, copy handle, rows, meta, polls seen]
-        self._seq = 0
         self._rows = []       # (iteration, time, the combined raw row)
         self.file = cfg.prefix + ".csv" if m.is_root() else None
         if self.file is not None:
@@ -215,13 +207,12 @@ class Diagnostics:
                 with open(self.file, "w") as fh:
                     fh.write(format_header(self.columns))
 
-    # ------------------------------------------------------------ taking a sample
-    def _buffers(self):
-        if self._tab is None:
-            n, dev = self.cfg.flush_every * NSLOT, self.solver.backend.device
-            self._tab = [torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(2)]
-            self._host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
+    @property
+    def sync_count(self):
+        """how often a row had to wait for a table whose copy had not been landed"""
+        return self.ring.waits
 
+    # ------------------------------------------------------------ taking a sample
     def reduce(self, u, v, w, grads, out=None):
         """the raw row of u, v, w and nine gradient fields of the caller's (compute_vorticity's order) -> `out`, a device
         float64 tensor of 16 values (default: a scratch row of this object), which is returned; slots 7 and 13 keep what
@@ -240,11 +231,9 @@ class Diagnostics:
         """one row for iteration `it` into the current device table from fields of the caller's: the reduction over u, v,
         w and the nine gradients and, if div_u is given, the max / sum of that block; no host wait unless both tables
         are in flight"""
-        self._buffers()
-        k = self._cur
-        if self._count == 0 and self._pending[k] is not None:  # a third table before the first has landed
-            self._land(k, count_wait=True)
-        row = self._tab[k][self._count * NSLOT:(self._count + 1) * NSLOT]
+        if self._count == 0:  # (a third table before the first has landed waits here)
+            self._slot = self.ring.acquire(self.cfg.flush_every * NSLOT * 8)
+        row = self._slot.dev.view(torch.float64)[self._count * NSLOT:(self._count + 1) * NSLOT]
         self.reduce(u, v, w, grads, out=row)
         if div_u is not None:
             self.solver.backend.diag_max_sum(div_u, row.data_ptr())
@@ -257,14 +246,9 @@ class Diagnostics:
     def sample(self, it):
         """one row for iteration `it` from the solver's velocity: nine gradients, the reduction, the divergence"""
         s = self.solver
-        b, al = s.backend, s.backend.allocator
+        al = s.backend.allocator
         s.flush_grad()  # a velocity correction left pending by step(more=True) is not in u, v, w yet
-        taken = []
-        for f in (s.u, s.v, s.w):
-            for dirps, d in ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z)):
-                g = al.get_block(DIR_X, VERT)
-                b.tds_apply(g, f, dirps.der1st, d)
-                taken.append(g)
+        taken = s.velocity_gradients()
         div_u = None
         if self.cfg.divergence:
             div_u = al.get_block(DIR_Z)
@@ -275,9 +259,13 @@ class Diagnostics:
         for g in taken:  # (stream-ordered: whoever takes them next writes behind the reductions)
             al.release_block(g)
 
+    def reads_state(self, it):
+        """does update(it) read the solver's fields?  (BaseCase.run then completes the step first)"""
+        return self.cfg.sample_due(it)
+
     def update(self, it):
         """one sample if iteration `it` is due; returns whether one was taken.  No host wait."""
-        if not self.cfg.sample_due(it):
+        if not self.reads_state(it):
             return False
         self.sample(it)
         return True
@@ -287,24 +275,16 @@ class Diagnostics:
         """start the copy of the current table's rows (if it has any) and go on with the other table; no host wait"""
         if self._count == 0:
             return False
-        k, n = self._cur, self._count
-        h = self.solver.backend.snapshot_copy_async(self._host[k], self._tab[k], n * NSLOT * 8)
-        self._seq += 1
-        self._pending[k] = [self._seq, h, n, self._meta[:n].copy(), 0]
+        n = self._count
+        self.ring.submit(self._slot, n * NSLOT * 8, [n, self._meta[:n].copy(), 0])  # (rows, meta, polls seen)
         self._count = 0
-        self._cur ^= 1
         return True
 
-    def _land(self, k, count_wait=False):
-        """table k's copy -> rows and lines; waits for the copy if it has not landed"""
+    def _land(self, payload, raw):
+        """the ring's landing: a table's bytes -> rows and lines; returns the rows added"""
         b = self.solver.backend
-        _, h, n, meta, _ = self._pending[k]
-        if not b.snapshot_done(h):
-            b.snapshot_wait(h)
-            if count_wait:
-                self.sync_count += 1
-        raw = self._host[k].numpy()[:n * NSLOT].reshape(n, NSLOT).copy()
-        self._pending[k] = None
+        n, meta, _ = payload
+        raw = raw.view(np.float64).reshape(n, NSLOT).copy()
         if b.comm.size > 1:
             sums, maxs = torch.from_numpy(raw[:, SUM_SLOTS].copy()), torch.from_numpy(raw[:, MAX_SLOTS].copy())
             b.comm.allreduce_tensor(sums, "sum")
@@ -319,32 +299,23 @@ class Diagnostics:
                 fh.writelines(lines)
         return n
 
-    def _in_flight(self):
-        return sorted((p[0], k) for k, p in enumerate(self._pending) if p is not None)
-
     def poll(self):
         """turn the tables whose copies have landed into rows, oldest first; returns the rows added.  One rank: never
         blocks.  Several ranks: a table is landed by the second poll after its flush (see the module docstring)."""
-        b = self.solver.backend
+        if self.solver.backend.comm.size == 1:
+            return sum(self.ring.poll())
         n = 0
-        for _, k in self._in_flight():
-            p = self._pending[k]
-            p[4] += 1
-            if b.comm.size > 1:
-                if p[4] < 2:
-                    break
-            elif not b.snapshot_done(p[1]):
+        for slot, p in self.ring.pending():
+            p[2] += 1
+            if p[2] < 2:
                 break
-            n += self._land(k)
+            n += self.ring.land(slot)
         return n
 
     def finalise(self):
         """flush, then wait for and write what is left"""
         self.flush()
-        n = 0
-        for _, k in self._in_flight():
-            n += self._land(k)
-        return n
+        return sum(self.ring.drain())
 
     # ------------------------------------------------------------ results
     def _derive(self, raw):

@@ -7,8 +7,8 @@ asked for) and the vertex pressure with the operators of compute_derived_fields 
 Cartesian layout, then launches ONE kernel that decimates, converts and packs every variable into a dense device buffer
 (HipBackend.snapshot_pack, csrc/snapshot.hip; |omega| and Q at the kept points only) and ONE asynchronous copy of that
 buffer into pinned host memory on a second stream.  `write` returns without a host wait; `poll` writes the files of the
-copies that have landed, `finalise` waits for the rest.  Two device and two host buffers: a third snapshot that arrives
-before the first has been written waits for it.
+copies that have landed, `finalise` waits for the rest.  The buffers are a ring of 2 slots (copyring.CopyRing): the 3rd
+acquire waits, that is, a third snapshot that arrives before the first has been written waits for it.
 
 Which points are kept.  The reference strides each rank's block from the rank's own first point
 (io_field_utils.f90:122, 175-188).  Here a point is kept where its GLOBAL index (0-based) is a multiple of the stride:
@@ -30,10 +30,10 @@ import glob
 import os
 
 import numpy as np
-import torch
 
 from . import _lib
 from .common import DIR_X, DIR_Y, DIR_Z, VERT, X3dError
+from .copyring import CopyRing
 
 # output_fields of checkpoint_params (src/config.f90), in the order get_snapshot_fields tests them
 OUTPUT_FIELDS = ("pressure", "vorticity", "qcriterion", "ibm", "species")
@@ -124,15 +124,6 @@ def generate_vtk_xml(dims, fields, origin, spacing):
     return xml
 
 
-class _Slot:
-    """one packed device buffer + its pinned host twin; pending = (iteration, handle) while a copy is unwritten"""
-
-    def __init__(self, nbytes, device):
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        self.pending = None
-
-
 class Snapshots:
     """Snapshots(solver, cfg), attached as `case.snapshots = Snapshots(case.solver, cfg)`: BaseCase.run then calls
     write(it) and poll() once per step and finalise() before it returns."""
@@ -160,63 +151,48 @@ class Snapshots:
         self.origin = tuple(float(m.vert_coords[d][0]) - int(m.n_offset[d]) * float(m.d[d]) for d in range(3))
         self.spacing = tuple(float(m.d[d]) * cfg.output_stride[d] for d in range(3))
         self.vtk_xml = generate_vtk_xml(self.shape, self.names, self.origin, self.spacing)
-        self._slots = None  # made by the first due write: an attached but idle Snapshots takes nothing
-        self._next = 0
+        # (an attached but idle Snapshots takes nothing; the geometry above needs no backend at all)
+        self.ring = CopyRing(getattr(solver, "backend", None), 2, self._write_file)
         self._ep1 = None    # device copy of the immersed boundary's mask, made when "ibm" is first written
         self.files = []     # names of the files written so far
         if cfg.has("pressure"):
             solver.keep_pressure = True  # base_case.f90:119-121
 
     # ------------------------------------------------------------ taking a snapshot
+    def reads_state(self, it):
+        """does write(it) read the solver's fields?  (BaseCase.run then completes the step first)"""
+        return self.cfg.due(it)
+
     def write(self, it):
         """if iteration `it` is due: gradients / vertex pressure, one pack launch, one asynchronous copy; returns
         whether a snapshot was taken.  No host wait unless both buffers still hold unwritten snapshots."""
-        if not self.cfg.due(it):
+        if not self.reads_state(it):
             return False
         s = self.solver
         b, al = s.backend, s.backend.allocator
         s.flush_grad()  # a velocity correction left pending by step(more=True) is not in u, v, w yet
-        if self._slots is None:
-            self._slots = [_Slot(self.nbytes, b.device) for _ in range(2)]
-        slot = self._slots[self._next]
-        if slot.pending is not None:  # the third snapshot before the first was written
-            b.snapshot_wait(slot.pending[1])
-            self._write_file(slot)
-        taken = []
-
-        def block():
-            f = al.get_block(DIR_X, VERT)
-            taken.append(f)
-            return f
-
+        slot = self.ring.acquire(self.nbytes)  # (the third snapshot before the first was written waits here)
         grads = None
         if self.cfg.has("vorticity") or self.cfg.has("qcriterion"):
-            # the operators of compute_derived_fields (postprocess.f90:47-127), no reorders: dudx, dudy, dudz, dvdx, ...
-            grads = []
-            for f in (s.u, s.v, s.w):
-                for dirps, d in ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z)):
-                    g = block()
-                    b.tds_apply(g, f, dirps.der1st, d)
-                    grads.append(g)
+            grads = s.velocity_gradients()
+        taken = list(grads or ())
         variables = []
         for name in self.names:
             if name in ("u", "v", "w"):
                 variables.append(("copy", getattr(s, name), 1.0))
             elif name == "p":
-                variables.append(("copy", self._pressure_vert(block(), block()), 1.0 / s.dt))
-            elif name == "vort":
-                variables.append(("vort", grads))
-            elif name == "qcrit":
-                variables.append(("qcrit", grads))
+                taken += [al.get_block(DIR_X, VERT), al.get_block(DIR_X, VERT)]
+                variables.append(("copy", self._pressure_vert(*taken[-2:]), 1.0 / s.dt))
+            elif name in ("vort", "qcrit"):
+                variables.append((name, grads))
             elif name == "ibm":
                 variables.append(("copy", self._ep1_block(), 1.0))
             else:
                 variables.append(("copy", s.species[int(name[4:]) - 1], 1.0))
         n = b.snapshot_pack(variables, self.first, self.cfg.output_stride, self.count, slot.dev, self.dtype)
-        slot.pending = (int(it), b.snapshot_copy_async(slot.host, slot.dev, n))
+        self.ring.submit(slot, n, int(it))
         for f in taken:  # (stream-ordered: whoever takes them next writes behind the pack)
             al.release_block(f)
-        self._next ^= 1
         return True
 
     def _pressure_vert(self, t1, t2):
@@ -248,10 +224,10 @@ class Snapshots:
         m = self.solver.mesh
         return "%s_%06d%s.npz" % (self.cfg.snapshot_prefix, it, "" if m.nproc == 1 else ".r%d" % m.nrank)
 
-    def _write_file(self, slot):
-        it, _ = slot.pending
+    def _write_file(self, it, raw):
+        """the ring's landing: the file of iteration `it` from the packed bytes"""
         cx, cy, cz = self.count
-        a = slot.host.numpy()[:self.nbytes].view(self.dtype).reshape(len(self.names), cz, cy, cx)
+        a = raw.view(self.dtype).reshape(len(self.names), cz, cy, cx)
         out = {name: a[k] for k, name in enumerate(self.names)}
         out.update({"time": np.float64(it * self.solver.dt), "iteration": np.int64(it),
                     "stride": np.array(self.cfg.output_stride, dtype=np.int64),
@@ -260,31 +236,16 @@ class Snapshots:
                     "spacing": np.array(self.spacing), "vtk.xml": np.array(self.vtk_xml)})
         name = self._file_name(it)
         np.savez(name, **out)
-        slot.pending = None
         self.files.append(name)
         return name
 
-    def _oldest_first(self):
-        if self._slots is None:
-            return []
-        return [self._slots[self._next], self._slots[self._next ^ 1]]
-
     def poll(self):
         """write every snapshot whose copy has landed (oldest first); never blocks.  Returns the files written."""
-        out = []
-        for slot in self._oldest_first():
-            if slot.pending is not None and self.solver.backend.snapshot_done(slot.pending[1]):
-                out.append(self._write_file(slot))
-        return out
+        return self.ring.poll()
 
     def finalise(self):
         """wait for and write what is left"""
-        out = []
-        for slot in self._oldest_first():
-            if slot.pending is not None:
-                self.solver.backend.snapshot_wait(slot.pending[1])
-                out.append(self._write_file(slot))
-        return out
+        return self.ring.drain()
 
 
 def load_snapshot(prefix, it):

@@ -617,6 +617,19 @@ class Solver:
         self.vector_calculus.curl(o_i_hat, o_j_hat, o_k_hat, u, v, w, self.xdirps.der1st,
                                   self.ydirps.der1st, self.zdirps.der1st)
 
+    def velocity_gradients(self):
+        """the nine first derivatives of u, v, w on DIR_X, VERT pool blocks: the operators of compute_derived_fields
+        (postprocess.f90:47-127) with no reorders, in compute_vorticity's order (dudx, dudy, dudz, dvdx, ...).  The caller
+        releases the blocks."""
+        b = self.backend
+        grads = []
+        for f in (self.u, self.v, self.w):
+            for dirps, d in ((self.xdirps, DIR_X), (self.ydirps, DIR_Y), (self.zdirps, DIR_Z)):
+                g = b.allocator.get_block(DIR_X, VERT)
+                b.tds_apply(g, f, dirps.der1st, d)
+                grads.append(g)
+        return grads
+
     # ---- :653-691
     def poisson_fft(self, pressure, div_u):
         b, al = self.backend, self.backend.allocator

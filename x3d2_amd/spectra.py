@@ -27,7 +27,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .common import VERT, X3dError
+from .common import VERT, X3dError, sample_due
 
 MODES = ("shell", "plane")
 MAXBINS = 4096
@@ -61,13 +61,7 @@ class SpectraConfig:
         return self.initspec > 0
 
     def sample_due(self, it):
-        if not self.active:
-            return False
-        if it < self.initspec:
-            return False
-        if (it - self.initspec) % self.ispecfreq != 0:
-            return False
-        return True
+        return sample_due(it, self.initspec, self.ispecfreq)
 
     due = sample_due
 
@@ -279,10 +273,14 @@ class Spectra:
                 raise X3dError("Spectra: field `%s` must be at VERT" % name)
             _lib.check(b.lib.x3d_spectra_sample(self.h, ph, f.ptr, slot))
 
+    def reads_state(self, it):
+        """does update(it) read the solver's fields?  (BaseCase.run then completes the step first)"""
+        return self.cfg.sample_due(it)
+
     def update(self, it):
         """one sample if iteration `it` is due: every field's spectrum, then the running means; returns whether one was
         taken.  No host wait."""
-        if not self.cfg.sample_due(it):
+        if not self.reads_state(it):
             return False
         self.sample()
         self.sample_count += 1

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .common import DIR_X, VERT, X3dError
+from .common import DIR_X, VERT, X3dError, sample_due
 
 # accumulator names in moment order (src/io/stats.f90:34-43, 151-159)
 MEAN_NAMES = ("umean", "vmean", "wmean", "uumean", "vvmean", "wwmean", "uvmean", "uwmean", "vwmean")
@@ -42,13 +42,7 @@ class StatsConfig:
 
     def sample_due(self, it):
         """src/io/stats.f90:129-131"""
-        if not self.active:
-            return False
-        if it < self.initstat:
-            return False
-        if (it - self.initstat) % self.istatfreq != 0:
-            return False
-        return True
+        return sample_due(it, self.initstat, self.istatfreq)
 
     def output_due(self, it):
         """src/io/stats.f90:211-213"""
@@ -100,9 +94,13 @@ class Stats:
         return f
 
     # ------------------------------------------------------------ sampling
+    def reads_state(self, it):
+        """does update(it) read the solver's fields?  (BaseCase.run then completes the step first)"""
+        return self.cfg.sample_due(it)
+
     def update(self, it):
         """one sample if iteration `it` is due (src/io/stats.f90:118-187); returns whether one was taken"""
-        if not self.cfg.sample_due(it):
+        if not self.reads_state(it):
             return False
         s = self.solver
         b = s.backend
