@@ -206,7 +206,7 @@ extern "C" int x3d_diag_reduce(x3d_backend *b, const real_t *u, const real_t *v,
 
 // ---------------------------------------------------------------- max |f| and sum |f| of one block
 // Stage 1 is x3d_field_max_sum's own launch (backend.hip); stage 2 does on the device what that entry point does on the host:
-// the partial sums added in index order in the real kind, so the two give the same bits.
+// the partial sums added in index order in double and rounded to the real kind, so the two give the same bits.
 __global__ void __launch_bounds__(256) k_diag_finish_max_sum(const real_t *__restrict__ part_sum, const real_t *__restrict__ part_max,
                                                              int nparts, double *__restrict__ row)
 {
@@ -217,10 +217,10 @@ __global__ void __launch_bounds__(256) k_diag_finish_max_sum(const real_t *__res
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        real_t s = 0.0;
+        double s = 0.0;  // (in double in either flavour, as run_reduce's host loop)
 #pragma unroll 8
-        for (int p = 0; p < nparts; p++) s += ps[p];
-        row[7] = (double)s;
+        for (int p = 0; p < nparts; p++) s += (double)ps[p];
+        row[7] = (double)(real_t)s;
     } else if (threadIdx.x == 64) {
         real_t m = 0.0;
 #pragma unroll 8
