@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -47,6 +47,13 @@ and x3d_scalar_product on the same box; (b) a whole Diagnostics sample -- nine g
 its max / sum -- as wall clock around a device sync; (c) Monitoring.write_step + kinetic_energy on the same state in the
 same process, the same way, with the host waits of each (x3d_backend_counter 3); (d) a 20-step TGV run with idiagfreq = 1
 against the same run without: added wall time per step.  The lines are appended to profiles/diagnostics.jsonl.
+
+Family "budgets" (--snap-n^3 = 512^3, median of --stat-iters with the quartiles as spread; not part of "all"): (a) the
+x3d_budget_profile_sums launches alone (HIP events) in GB/s on the thirteen blocks they read (104 B/DoF in FP64), next to
+x3d_diag_reduce (96 B/DoF) in the same process, and the gate t_budget <= 1.25 (104 / 96) t_diag_reduce; (b) a whole
+Budgets.update as wall clock around a device sync; (c) the composed host path in the same process, thirteen get_field_data
+plus numpy moments; (d) a 20-step TGV run with ibudfreq = 1, pressure = False against the same run without: added wall time
+per step.  The lines are appended to profiles/budgets.jsonl.
 """
 import argparse
 import json
@@ -517,9 +524,40 @@ def bench_spectra(args):
     row("spectra: three-field plane sample (3 2-D transforms + 3 reductions + mean)", dims, t, tmin, k)
 
 
+def spread(times):
+    q1, med, q3 = (float(v) for v in np.percentile(times, [25, 50, 75]))
+    return {"ms_median": med, "ms_q1": q1, "ms_q3": q3, "ms_min": float(min(times)), "samples": len(times)}
+
+
+def timed_events(args, b, fn):
+    """HIP-event ms of fn() on the backend's stream: --stat-iters samples after --stat-warmup"""
+    import ctypes
+    from x3d2_amd import _lib
+    ms, times = ctypes.c_float(), []
+    for i in range(args.stat_warmup + args.stat_iters):
+        _lib.check(b.lib.x3d_timer_start(b.h))
+        fn()
+        _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+        if i >= args.stat_warmup:
+            times.append(ms.value)
+    return times
+
+
+def timed_wall(args, b, fn):
+    """wall-clock ms of fn() between two device syncs"""
+    times = []
+    for i in range(args.stat_warmup + args.stat_iters):
+        b.sync()
+        t0 = time.perf_counter()
+        fn()
+        b.sync()
+        if i >= args.stat_warmup:
+            times.append((time.perf_counter() - t0) * 1e3)
+    return times
+
+
 def bench_diagnostics(args):
     """one JSON line per measurement of the "diagnostics" family, printed and appended to profiles/diagnostics.jsonl"""
-    import ctypes
     import tempfile
 
     import torch
@@ -536,31 +574,7 @@ def bench_diagnostics(args):
         with open(out_path, "a") as fh:
             fh.write(line + "\n")
 
-    def spread(times):
-        q1, med, q3 = (float(v) for v in np.percentile(times, [25, 50, 75]))
-        return {"ms_median": med, "ms_q1": q1, "ms_q3": q3, "ms_min": float(min(times)), "samples": len(times)}
-
-    def events(b, fn):
-        ms, times = ctypes.c_float(), []
-        for i in range(args.stat_warmup + args.stat_iters):
-            _lib.check(b.lib.x3d_timer_start(b.h))
-            fn()
-            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
-            if i >= args.stat_warmup:
-                times.append(ms.value)
-        return times
-
-    def wall(b, fn):
-        times = []
-        for i in range(args.stat_warmup + args.stat_iters):
-            b.sync()
-            t0 = time.perf_counter()
-            fn()
-            b.sync()
-            if i >= args.stat_warmup:
-                times.append((time.perf_counter() - t0) * 1e3)
-        return times
-
+    events, wall = (lambda b, fn: timed_events(args, b, fn)), (lambda b, fn: timed_wall(args, b, fn))
     case = make_tgv(n, fused=True)
     s = case.solver
     b, al = s.backend, s.backend.allocator
@@ -623,6 +637,103 @@ def bench_diagnostics(args):
           "added_ms_per_step": (res[True] - res[False]) / 20.0})
 
 
+def bench_budgets(args):
+    """one JSON line per measurement of the "budgets" family, printed and appended to profiles/budgets.jsonl"""
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.budgets import Budgets, BudgetsConfig
+    from x3d2_amd.common import DIR_X, VERT
+    from x3d2_amd.diagnostics import Diagnostics, DiagnosticsConfig
+    import tempfile
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    tmp = tempfile.mkdtemp(prefix="x3d_bud_")
+    out_path = os.path.join(ROOT, "profiles", "budgets.jsonl")
+
+    def emit(row):
+        row = dict({"family": "budgets", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    events, wall = (lambda b, fn: timed_events(args, b, fn)), (lambda b, fn: timed_wall(args, b, fn))
+    case = make_tgv(n, fused=True)
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    case.step(1)
+    s.flush_grad()
+    bud = Budgets(s, BudgetsConfig(initbud=1, profile_dir=2, pressure=False, prefix=os.path.join(tmp, "b")))
+    dg = Diagnostics(s, DiagnosticsConfig(prefix=os.path.join(tmp, "a")))
+    # (a) the sums launches alone, on gradients computed once and a thirteenth block in the pressure's place, next to
+    # x3d_diag_reduce in the same process: both are read-only streams
+    grads = s.velocity_gradients()
+    p = al.get_block(DIR_X, VERT)
+    b.veccopy(p, s.u)
+    tb = spread(events(b, lambda: b.budget_profile_sums(s.u, s.v, s.w, p, grads, 2, 1.0 / s.dt, bud.sums)))
+    nbytes = 13 * rb * n ** 3
+    emit(dict({"op": "x3d_budget_profile_sums: both launches (13 blocks read)", "bytes": nbytes,
+               "GBs": nbytes / tb["ms_median"] / 1e6, "ceiling": nbytes / tb["ms_median"] / 1e6 / 6200.0,
+               "row_pitch": b.padded_dims[0]}, **tb))
+    td = spread(events(b, lambda: dg.reduce(s.u, s.v, s.w, grads)))
+    nbytes = 12 * rb * n ** 3
+    emit(dict({"op": "x3d_diag_reduce: both launches (12 blocks read)", "bytes": nbytes, "GBs": nbytes / td["ms_median"] / 1e6,
+               "ceiling": nbytes / td["ms_median"] / 1e6 / 6200.0}, **td))
+    limit = 1.25 * (104.0 / 96.0) * td["ms_median"]
+    emit({"op": "gate: t_budget <= 1.25 (104 / 96) t_diag_reduce", "budget_ms_median": tb["ms_median"],
+          "diag_reduce_ms_median": td["ms_median"], "ratio": tb["ms_median"] / td["ms_median"], "limit_ms": limit,
+          "passed": bool(tb["ms_median"] <= limit)})
+    al.release_block(p)
+    for g in grads:
+        al.release_block(g)
+    # (b) a whole update (no pressure: a TGV run keeps none), (c) the composed host path it replaces: thirteen
+    # get_field_data plus numpy moments; wall clock around a device sync, same state, same process
+    tu = spread(wall(b, sample_of(bud)))
+    emit(dict({"op": "Budgets.update, pressure=False: 9 gradients + sums + recurrence (wall clock)"}, **tu))
+
+    def host_path():
+        taken = s.velocity_gradients() + [al.get_block(DIR_X, VERT)]
+        a = [b.get_field_data(f) for f in [s.u, s.v, s.w] + taken]
+        for f in taken:
+            al.release_block(f)
+        vel, pp, g = a[:3], a[12], [a[3:6], a[6:9], a[9:12]]
+        pairs = ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))
+        mean = lambda x: x.mean(axis=(0, 2))
+        out = [mean(x) for x in vel] + [mean(pp)] + [mean(pp * pp)] + [mean(pp * x) for x in vel]
+        for i, j in pairs:
+            uu = vel[i] * vel[j]
+            out += [mean(uu), mean(uu * vel[1]), mean(g[i][0] * g[j][0] + g[i][1] * g[j][1] + g[i][2] * g[j][2]),
+                    mean(pp * (g[i][j] + g[j][i]))]
+        out += [mean(x) for row in g for x in row]
+        return out
+
+    saved = args.stat_warmup, args.stat_iters
+    args.stat_warmup, args.stat_iters = 0, 3  # (seconds per call)
+    th = spread(wall(b, host_path))
+    args.stat_warmup, args.stat_iters = saved
+    emit(dict({"op": "composed host path: 13 get_field_data + numpy moments (wall clock)"}, **th))
+    emit({"op": "gate: update faster than the composed host path", "update_ms_median": tu["ms_median"],
+          "host_ms_median": th["ms_median"], "passed": bool(tu["ms_median"] < th["ms_median"])})
+    del case, s, b, al, bud, dg, grads, p
+    torch.cuda.empty_cache()
+    # (d) a 20-step run with a sample per step against the same run without
+    res = {}
+    for with_bud in (False, True):
+        case = make_tgv(n, fused=True)
+        if with_bud:
+            case.budgets = Budgets(case.solver, BudgetsConfig(initbud=1, ibudfreq=1, pressure=False,
+                                                              prefix=os.path.join(tmp, "d")))
+        case.run(n_iters=3)
+        case.solver.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        case.solver.backend.sync()
+        res[with_bud] = (time.perf_counter() - t0) * 1e3
+        del case
+        torch.cuda.empty_cache()
+    emit({"op": "TGV, fused, RK3: 20 steps, ibudfreq 1, pressure=False", "wall_ms_without": res[False],
+          "wall_ms_with": res[True], "added_ms_per_step": (res[True] - res[False]) / 20.0})
+
+
 def sample_of(sp):
     count = [sp.sample_count]
 
@@ -638,7 +749,8 @@ def main():
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics"))
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics",
+                                                               "budgets"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -655,7 +767,9 @@ def main():
         bench_spectra(args)
     if args.family == "diagnostics":
         bench_diagnostics(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics"):
+    if args.family == "budgets":
+        bench_budgets(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets"):
         return
     import torch
     from x3d2_amd import Mesh

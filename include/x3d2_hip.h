@@ -880,6 +880,30 @@ int x3d_diag_reduce(x3d_backend *b, const x3d_real *u, const x3d_real *v, const 
  * row_dev[13] = max |f|, row_dev[7] = sum |f| */
 int x3d_diag_max_sum(x3d_backend *b, const x3d_real *f, const int dims[3], double *row_dev);
 
+/* ---- Reynolds-stress budget profiles on the device (csrc/budget.hip).  Not in the reference: this project's own addition,
+ * like the profile mode of the statistics.  One pass over u, v, w, the vertex pressure and the nine velocity gradients
+ * (104 B/DoF in FP64) leaves the plane sums of 41 raw moments along dir_keep (2 or 3; 1 is not built: an error).  With
+ * d = dir_keep - 1, g_ij = grads[3 i + j], p = p_scale * f->p and the pairs in the order (uu, vv, ww, uv, uw, vw):
+ *    0..2   u, v, w               3  p                    4..9   u_i u_j          10  p p          11..13  p u, p v, p w
+ *    14..19 u_i u_j u_d           20..28  g_ij            29..34 sum_k g_ik g_jk  35..40  p (g_ij + g_ji)
+ * Every factor is converted to double before any product; partials, sums and prof are double in BOTH flavours (central triple
+ * and gradient moments are differences of raw moments).  f->p = NULL: nothing is loaded for p and moments 3, 10..13 and 35..40
+ * are exactly 0.  Two stages, deterministic: per kept index and part, partial sums in a fixed order, added in part order by a
+ * second small launch; no floating-point atomics; the launch geometry depends on dims and dir_keep alone.  Ordered on the
+ * backend's stream, no host wait; a bad argument is an error and launches nothing. */
+#define X3D_NBUDGET 41
+typedef struct x3d_budget_fields {
+    const x3d_real *u, *v, *w;
+    const x3d_real *p;        /* vertex pressure block, or NULL: the pressure moments stay 0 */
+    const x3d_real *grads[9]; /* x3d_compute_vorticity's order, as x3d_diag_reduce takes them */
+} x3d_budget_fields;
+/* sums[m][q] (device, 41 * dims[dir_keep - 1] doubles) = the sum of moment m over the unpadded extent dims of the two
+ * directions other than dir_keep, for every index q along it */
+int x3d_budget_profile_sums(x3d_backend *b, const x3d_budget_fields *f, const int dims[3], int dir_keep, double p_scale,
+                            double *sums);
+/* prof[i] += (sums[i] * scale - prof[i]) * inc, i < n, in double: accumulate_mean on the plane means */
+int x3d_budget_profile_accumulate(x3d_backend *b, double *prof, const double *sums, long n, double scale, double inc);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

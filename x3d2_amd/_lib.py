@@ -259,6 +259,8 @@ PROTOTYPES = {
     "x3d_spectra_load": (I, [VP, ctypes.POINTER(ctypes.c_double)]),
     "x3d_diag_reduce": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), c_int_p, VP, VP]),
     "x3d_diag_max_sum": (I, [VP, VP, c_int_p, VP]),
+    "x3d_budget_profile_sums": (I, [VP, VP, c_int_p, I, ctypes.c_double, VP]),
+    "x3d_budget_profile_accumulate": (I, [VP, VP, VP, ctypes.c_long, ctypes.c_double, ctypes.c_double]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),
@@ -277,6 +279,11 @@ class SnapshotVar(ctypes.Structure):
 class DiagParams(ctypes.Structure):
     """x3d_diag_params of include/x3d2_hip.h"""
     _fields_ = [("ih_x", VP), ("ih_y", VP), ("ih_z", VP), ("first_y", I), ("last_y", I)]
+
+
+class BudgetFields(ctypes.Structure):
+    """x3d_budget_fields of include/x3d2_hip.h"""
+    _fields_ = [("u", VP), ("v", VP), ("w", VP), ("p", VP), ("grads", VP * 9)]
 
 
 _lib = None

@@ -1149,6 +1149,33 @@ class HipBackend:
         self.red_epoch += 1
         _lib.check(self.lib.x3d_diag_max_sum(self.h, f.ptr, self._dims(loc), VP(int(row_ptr))))
 
+    # ------------------------------------------------------------ budget profiles (csrc/budget.hip)
+    NBUDGET = 41  # X3D_NBUDGET of include/x3d2_hip.h
+
+    def budget_profile_sums(self, u, v, w, p, grads, dir_keep, p_scale, sums):
+        """sums (device float64 tensor of 41 * n_keep values) <- the plane sums of the 41 raw budget moments (the table of
+        include/x3d2_hip.h) over this rank's share of the two directions other than dir_keep (2 or 3), from u, v, w, the
+        vertex pressure p (scaled by p_scale; None: the pressure moments stay 0) and the nine gradient fields
+        (compute_vorticity's order) in one pass.  Rank-local, no host synchronisation."""
+        if len(grads) != 9:
+            raise X3dError("budget_profile_sums: nine gradient fields expected")
+        self._need_vert("budget_profile_sums", u, v, w, *grads)
+        if dir_keep not in (DIR_Y, DIR_Z):
+            raise X3dError("budget_profile_sums: dir_keep must be 2 or 3 (1 is not built)")
+        if sums.dtype != torch.float64 or not sums.is_cuda or \
+                sums.numel() < self.NBUDGET * self.mesh.get_dims(VERT)[dir_keep - 1]:
+            raise X3dError("budget_profile_sums: sums is a device float64 tensor of 41 * n_keep values")
+        f = _lib.BudgetFields(u.ptr, v.ptr, w.ptr, None if p is None else p.ptr, (VP * 9)(*[g.ptr for g in grads]))
+        _lib.check(self.lib.x3d_budget_profile_sums(self.h, ctypes.byref(f), self._dims(VERT), int(dir_keep),
+                                                    float(p_scale), sums.data_ptr()))
+
+    def budget_profile_accumulate(self, prof, sums, scale, inc):
+        """prof += (sums * scale - prof) * inc on two device float64 tensors of equal size"""
+        if prof.numel() != sums.numel() or prof.dtype != torch.float64 or sums.dtype != torch.float64:
+            raise X3dError("budget_profile_accumulate: prof and sums are float64 tensors of equal size")
+        _lib.check(self.lib.x3d_budget_profile_accumulate(self.h, prof.data_ptr(), sums.data_ptr(), prof.numel(),
+                                                          float(scale), float(inc)))
+
     # ------------------------------------------------------------ checkpoints (csrc/checkpoint.hip)
     CKPT_MAXBLOCK = 64  # X3D_CKPT_MAXBLOCK of include/x3d2_hip.h
 

@@ -56,6 +56,7 @@ class BaseCase:
         self.checkpoints = None
         # optional diagnostics.Diagnostics(solver, cfg, append=self.restarted): run() then samples, polls and finalises it
         self.diagnostics = None
+        self.budgets = None  # optional budgets.Budgets(solver, cfg): run() then samples and writes it (not in the reference)
         self.restarted = False
         self.step_times = []
         self.initial_conditions()
@@ -164,7 +165,7 @@ class BaseCase:
         """one time step.  more=True: another step follows at once and nothing looks at the fields in between, so
         the last sub-step's velocity correction may also wait for the next transeq_x kernel; whoever reads the
         velocity next without going through step() must call solver.flush_grad() first (run() does).
-        want_pressure: a snapshot of this step is due and solver.keep_pressure is set -- the fused driver then keeps
+        want_pressure: a snapshot or a budgets sample of this step is due and solver.keep_pressure is set -- the fused driver then keeps
         the pressure of the step's last sub-step (Solver.pressure_correction_fused)."""
         s = self.solver
         ns = s.time_integrator.nstage
@@ -182,13 +183,15 @@ class BaseCase:
         start = s.current_iter + 1
         for it in range(start, n_iters + 1):
             t0 = time.perf_counter()
-            diag, snap, ckpt = self.diagnostics, self.snapshots, self.checkpoints
-            # a statistics or spectra sample, a row of the diagnostics series, a snapshot (snapshot_manager.f90:125-126)
-            # and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step) read the velocity like an output step does
-            attached = [a for a in (self.stats, self.spectra, diag, snap, ckpt) if a is not None]
+            diag, snap, ckpt, bud = self.diagnostics, self.snapshots, self.checkpoints, self.budgets
+            # a statistics, spectra or budgets sample, a row of the diagnostics series, a snapshot
+            # (snapshot_manager.f90:125-126) and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step) read the
+            # velocity like an output step does
+            attached = [a for a in (self.stats, self.spectra, diag, bud, snap, ckpt) if a is not None]
             read = (s.n_output > 0 and it % s.n_output == 0) or any(a.reads_state(it) for a in attached)
             snap_due = snap is not None and snap.reads_state(it)
-            self.step(it, more=(it < n_iters and not read), want_pressure=snap_due and s.keep_pressure)
+            budgets_due = bud is not None and bud.pressure_due(it)  # (a budgets sample with pressure=True reads it too)
+            self.step(it, more=(it < n_iters and not read), want_pressure=(snap_due or budgets_due) and s.keep_pressure)
             s.current_iter = it
             if self.stats is not None:
                 self.stats.update(it)  # update_stats, base_case.f90:319
@@ -196,6 +199,8 @@ class BaseCase:
                 self.spectra.update(it)  # the transforms and the reductions; no host wait
             if diag is not None:
                 diag.update(it)  # nine gradients, one reduction into the device table; no host wait
+            if bud is not None:
+                bud.update(it)  # nine gradients, the vertex pressure, one reduction, the recurrence; no host wait
             if s.n_output > 0 and it % s.n_output == 0:
                 row = self.postprocess(it, it * s.dt)
                 if verbose and s.mesh.is_root():
@@ -205,6 +210,8 @@ class BaseCase:
                 self.stats.write(it)  # handle_io_step, base_case.f90:328
             if self.spectra is not None:
                 self.spectra.write(it)
+            if bud is not None:
+                bud.write(it)
             if snap is not None:
                 snap.write(it)  # packs and starts the copy; no host wait
                 snap.poll()     # files of the snapshots whose copies have landed

@@ -13,7 +13,8 @@ before the previous one has been written waits for it.
 The state, in this order: u, v, w; phi_<n> per species; for Adams-Bashforth of order > 1 `<name>_rhs_old<j>` for every
 variable in the integrator's list order (after its rotations); with active 3-D statistics their accumulators under
 Stats.state_dict's names (the profile mode's few KB go through state_dict on the host, and so do the running means of
-case.spectra under Spectra.state_dict's `spectra_*` names).
+case.spectra under Spectra.state_dict's `spectra_*` names and the budget profiles of case.budgets under
+Budgets.state_dict's `budgets_*` names).
 
 Scalars.  The reference's: timestep, time, dt, data_loc, ti_is_ab, ti_order, ti_istep, ti_nstep, stats_sample_count.
 Added here, because a resumed run must give the bits of the uninterrupted one:
@@ -114,6 +115,10 @@ class Checkpoints:
     def spectra(self):
         return getattr(self.case, "spectra", None) if self.case is not None else None
 
+    @property
+    def budgets(self):
+        return getattr(self.case, "budgets", None) if self.case is not None else None
+
     def _file_name(self, it, tag=""):
         m = self.solver.mesh
         return file_name(self.cfg.checkpoint_prefix, it, m.nproc, m.nrank, tag)
@@ -141,6 +146,9 @@ class Checkpoints:
         sp = self.spectra
         if sp is not None and sp.cfg.active:  # the running means of the spectra: a few KB to a few MB, through the host
             out.update(sp.state_dict())
+        bud = self.budgets
+        if bud is not None and bud.cfg.active:  # the running budget profiles: 41 x n doubles, through the host
+            out.update(bud.state_dict())
         if self.case is not None:
             for k, v in self.case.checkpoint_state().items():
                 out["case_" + k] = np.asarray(v)
@@ -242,6 +250,9 @@ def restore(case, path):
     spectra = getattr(case, "spectra", None)
     if spectra is not None and not spectra.cfg.active:
         spectra = None
+    budgets = getattr(case, "budgets", None)
+    if budgets is not None and not budgets.cfg.active:
+        budgets = None
     # 2. does it fit?
     if int(z["precision"]) != REAL_BYTES:
         raise _differs("precision (bytes per real)", int(z["precision"]), REAL_BYTES)
@@ -282,6 +293,12 @@ def restore(case, path):
         if "spectra_sample_count" not in z:
             raise X3dError("restore: this run samples spectra, the checkpoint holds none")
         mean_from_state(z, spectra.cfg.mode, spectra.cfg.fields)  # (raises on another mode or other fields)
+    if budgets is not None:
+        from .budgets import moments_from_state
+        if "budgets_sample_count" not in z:
+            raise X3dError("restore: this run samples budgets, the checkpoint holds none")
+        # (raises on another profile_dir, another pressure setting or another length)
+        moments_from_state(z, budgets.cfg.profile_dir, budgets.cfg.pressure, budgets.n_keep_global)
     # 3. upload, 4. the checksums of what arrived, one host wait
     n = int(np.prod(dims))
     data, off, total = b.checkpoint_layout(len(names), n)
@@ -315,6 +332,8 @@ def restore(case, path):
         stats.sample_count = int(z["stats_sample_count"])
     if spectra is not None:
         spectra.load_state_dict(z)
+    if budgets is not None:
+        budgets.load_state_dict(z)
     case.load_checkpoint_state({k[5:]: v for k, v in z.items() if k.startswith("case_")})
     case.restarted = True
     return s.current_iter

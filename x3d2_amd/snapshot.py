@@ -32,7 +32,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .common import DIR_X, DIR_Y, DIR_Z, VERT, X3dError
+from .common import DIR_X, VERT, X3dError
 from .copyring import CopyRing
 
 # output_fields of checkpoint_params (src/config.f90), in the order get_snapshot_fields tests them
@@ -196,16 +196,8 @@ class Snapshots:
         return True
 
     def _pressure_vert(self, t1, t2):
-        """compute_pressure_vert (postprocess.f90:166-197) without the scale, which the pack applies: interpl_c2v =
-        interpl_p2v in z, y, x (src/vector_calculus.f90:334-378); returns the block that holds the result"""
-        s = self.solver
-        b = s.backend
-        if s.pressure is None:
-            raise X3dError("compute_pressure_vert: pressure not yet computed")
-        b.tds_apply(t1, s.pressure, s.zdirps.interpl_p2v, DIR_Z)
-        b.tds_apply(t2, t1, s.ydirps.interpl_p2v, DIR_Y)
-        b.tds_apply(t1, t2, s.xdirps.interpl_p2v, DIR_X)
-        return t1
+        """compute_pressure_vert without the scale, which the pack applies (Solver.pressure_vert)"""
+        return self.solver.pressure_vert(t1, t2)
 
     def _ep1_block(self):
         if self._ep1 is None:

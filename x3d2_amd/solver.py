@@ -630,6 +630,18 @@ class Solver:
                 grads.append(g)
         return grads
 
+    def pressure_vert(self, t1, t2):
+        """compute_pressure_vert (postprocess.f90:166-197) without the scale (1 / dt, which the caller applies): interpl_c2v
+        = interpl_p2v in z, y, x (src/vector_calculus.f90:334-378) through two DIR_X, VERT blocks of the caller's; returns
+        the block that holds the result"""
+        b = self.backend
+        if self.pressure is None:
+            raise X3dError("compute_pressure_vert: pressure not yet computed")
+        b.tds_apply(t1, self.pressure, self.zdirps.interpl_p2v, DIR_Z)
+        b.tds_apply(t2, t1, self.ydirps.interpl_p2v, DIR_Y)
+        b.tds_apply(t1, t2, self.xdirps.interpl_p2v, DIR_X)
+        return t1
+
     # ---- :653-691
     def poisson_fft(self, pressure, div_u):
         b, al = self.backend, self.backend.allocator
