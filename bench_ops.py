@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -54,6 +54,15 @@ x3d_diag_reduce (96 B/DoF) in the same process, and the gate t_budget <= 1.25 (1
 Budgets.update as wall clock around a device sync; (c) the composed host path in the same process, thirteen get_field_data
 plus numpy moments; (d) a 20-step TGV run with ibudfreq = 1, pressure = False against the same run without: added wall time
 per step.  The lines are appended to profiles/budgets.jsonl.
+
+Family "loads" (median of --stat-iters with the quartiles as spread; not part of "all"): on a 512 x 256 x 64 box with the
+default cylinder's proportions (20 x 12 x 6, diameter 1 through (L_x / 4, L_y / 2)), (a) x3d_ibm_body_loads, both launches,
+next to x3d_ibm_body on the same work list (HIP events), and how far the first lies above the second; (b) x3d_probe_sample
+for 256 probes; (c) 20 steps of make_cylinder((257, 128, 32), fused=True) with Loads at every step against the same run
+without, and (d) the same with Loads and Probes: wall time, the host waits (x3d_backend_counter 3) of each run during the
+steps and in finalise, and the launch groups of the per-class timers per sub-step (taken in a second, untimed run of 5 steps;
+with Loads they grow by exactly one, the finishing launch).  No gate on the times; the two counts are gates.  The lines are
+appended to profiles/loads.jsonl.
 """
 import argparse
 import json
@@ -744,12 +753,130 @@ def sample_of(sp):
     return sample
 
 
+def bench_loads(args):
+    """one JSON line per measurement of the "loads" family, printed and appended to profiles/loads.jsonl"""
+    import ctypes
+    import tempfile
+    from types import SimpleNamespace
+
+    import torch
+    from x3d2_amd import Mesh, _lib, make_cylinder
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.common import DIR_X, VERT
+    from x3d2_amd.ibm import Ibm, cylinder_mask
+    from x3d2_amd.loads import Loads, LoadsConfig, weights
+    from x3d2_amd.probes import Probes, ProbesConfig
+    rb = 4 if _lib.SINGLE else 8
+    tmp = tempfile.mkdtemp(prefix="x3d_loads_")
+    out_path = os.path.join(ROOT, "profiles", "loads.jsonl")
+    dims, L = (512, 256, 64), (20.0, 12.0, 6.0)
+
+    def emit(row):
+        row = dict({"family": "loads", "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    events = lambda b, fn: timed_events(args, b, fn)  # noqa: E731
+    mesh = Mesh(dims, (1, 1, 1), L, ("dirichlet",) * 2, ("periodic",) * 2, ("periodic",) * 2)
+    b = HipBackend(mesh)
+    al = b.allocator
+    u, v, w = (al.get_block(DIR_X, VERT) for _ in range(3))
+    rng = np.random.default_rng(0)
+    for f in (u, v, w):
+        b.set_field_data(f, 1.0 + 0.1 * rng.standard_normal(dims[::-1], dtype=np.float32))
+    ibm = Ibm(SimpleNamespace(backend=b), cylinder_mask(mesh, (L[0] / 4.0, L[1] / 2.0), 0.5))
+    dp = ctypes.POINTER(ctypes.c_double)
+    _lib.check(b.lib.x3d_ibm_set_weights(ibm.h, *[a.ctypes.data_as(dp) for a in weights(mesh)]))
+    row_dev = torch.zeros(4, dtype=torch.float64, device=b.device)
+    # (a) the body with and without the loads, alternating blocks of samples in one process
+    tb = spread(events(b, lambda: ibm.body(u, v, w)))
+    tl = spread(events(b, lambda: b.ibm_body_loads(ibm.h, u, v, w, row_dev.data_ptr(), 0)))
+    tb2 = spread(events(b, lambda: ibm.body(u, v, w)))
+    shape = {"dims": list(dims), "n_segments": ibm.n_segments, "n_masked": ibm.n_masked}
+    emit(dict({"op": "x3d_ibm_body (work list)", "ms_median_repeat": tb2["ms_median"]}, **shape, **tb))
+    emit(dict({"op": "x3d_ibm_body_loads: both launches", "above_body_ms": tl["ms_median"] - tb["ms_median"],
+               "over_body": tl["ms_median"] / tb["ms_median"]}, **shape, **tl))
+    # (b) 256 probes on a wake line and a cross line
+    pts = np.stack([np.linspace(5.5, 19.5, 256), 6.0 + 2.0 * np.sin(np.arange(256.0)), np.linspace(0.1, 5.9, 256)], axis=1)
+    stub = SimpleNamespace(backend=b, mesh=mesh, dt=0.0075, current_iter=0, u=u, v=v, w=w, flush_grad=lambda: None)
+    pr = Probes(stub, ProbesConfig(pts, prefix=os.path.join(tmp, "p")))
+    table = torch.zeros(3 * 256, dtype=torch.float64, device=b.device)
+    tp = spread(events(b, lambda: b.probe_sample(pr.h, u, v, w, table.data_ptr())))
+    emit(dict({"op": "x3d_probe_sample: 256 probes", "dims": list(dims)}, **tp))
+    del ibm, pr, stub, b, al, u, v, w, row_dev, table
+    torch.cuda.empty_cache()
+    # (c), (d) the case: 20 timed steps, then 5 steps of a fresh run under the per-class timers for the launch groups
+    cdims = (257, 128, 32)
+    wake = np.stack([np.linspace(5.5, 19.5, 256), np.full(256, 6.0), np.full(256, 3.0)], axis=1)
+
+    def attach(case, mode, tag):
+        if mode in ("loads", "loads+probes"):
+            case.loads = Loads(case.solver, LoadsConfig(prefix=os.path.join(tmp, tag + "_l")))
+        if mode == "loads+probes":
+            case.probes = Probes(case.solver, ProbesConfig(wake, prefix=os.path.join(tmp, tag + "_p")))
+
+    res = {}
+    for mode in ("none", "loads", "loads+probes"):
+        case = make_cylinder(cdims, fused=True)
+        sb = case.solver.backend
+        attach(case, mode, "t")
+        case.run(n_iters=3)  # (finalises what the three steps left: the timed run starts with empty tables)
+        sb.sync()
+        s0, t0 = sb.sync_count(), time.perf_counter()
+        n_steps = 20
+        # (run() opens with a postprocess row and closes with finalise(): the first waits the same way in every mode, the
+        #  second waits for the landings of what the 20 steps left in the tables)
+        case.run(n_iters=case.solver.current_iter + n_steps)
+        sb.sync()
+        wall = (time.perf_counter() - t0) * 1e3
+        res[mode] = {"wall_ms": wall, "ms_per_step": wall / n_steps, "stream_syncs": sb.sync_count() - s0,
+                     "ring_waits": sum(x.sync_count for x in (case.loads, case.probes) if x is not None),
+                     "rows": 0 if case.loads is None else int(len(case.loads.rows()))}
+        del case, sb
+        torch.cuda.empty_cache()
+        case = make_cylinder(cdims, fused=True)
+        sb = case.solver.backend
+        attach(case, mode, "c")
+        case.step(1)
+        sb.sync()
+        sb.prof_enable(True)
+        sb.prof_reset()
+        case.solver.current_iter = 1
+        for it in range(2, 7):
+            case.step(it, more=(mode != "loads+probes"))
+            case.solver.current_iter = it  # (as BaseCase.run does: Loads checks its count of body calls against it)
+            if case.probes is not None:
+                case.probes.update(it)
+        sb.sync()
+        groups = sum(sb.prof_get(k)[0] for k in sb.KINDS)
+        sb.prof_enable(False)
+        res[mode]["launch_groups_per_substep"] = groups / float(5 * case.solver.time_integrator.nstage)
+        del case, sb
+        torch.cuda.empty_cache()
+    base = res["none"]
+    for mode in ("none", "loads", "loads+probes"):
+        r = res[mode]
+        emit(dict({"op": "make_cylinder((257,128,32)), fused, AB3: 20 steps, " + mode, "dims": list(cdims),
+                   "added_ms_per_step": r["ms_per_step"] - base["ms_per_step"],
+                   "added_stream_syncs": r["stream_syncs"] - base["stream_syncs"],
+                   "added_launch_groups_per_substep": r["launch_groups_per_substep"] - base["launch_groups_per_substep"]}, **r))
+    # the landings finalise waits for: 20 rows at flush_every = 256 are one table per series
+    emit({"op": "gate: host waits with Loads = those without + the landings finalise waits for",
+          "added_stream_syncs": res["loads"]["stream_syncs"] - base["stream_syncs"], "landings_in_finalise": 1,
+          "passed": bool(res["loads"]["stream_syncs"] - base["stream_syncs"] == 1 and res["loads"]["ring_waits"] == 0)})
+    emit({"op": "gate: launches per sub-step grow by exactly one with Loads",
+          "added_launch_groups_per_substep": res["loads"]["launch_groups_per_substep"] - base["launch_groups_per_substep"],
+          "passed": bool(res["loads"]["launch_groups_per_substep"] - base["launch_groups_per_substep"] == 1.0)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics",
+    ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "loads",
                                                                "budgets"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
@@ -769,7 +896,9 @@ def main():
         bench_diagnostics(args)
     if args.family == "budgets":
         bench_budgets(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets"):
+    if args.family == "loads":
+        bench_loads(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads"):
         return
     import torch
     from x3d2_amd import Mesh

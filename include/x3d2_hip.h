@@ -744,6 +744,23 @@ int x3d_ibm_counts(const x3d_ibm *ibm, long out[2]);
  * same bits as three x3d_vecmult by the mask (x * 1.0 = x).  Padding and points outside dims are never written; dims must
  * be those of x3d_ibm_create.  An empty list returns without a launch. */
 int x3d_ibm_body(x3d_backend *b, const x3d_ibm *ibm, x3d_real *u, x3d_real *v, x3d_real *w, const int dims[3]);
+/* the quadrature weights of the loads: wx[nx], wy[ny], wz[nz] host doubles (this rank's slices), copied to the device and
+ * kept by the mask; a second call replaces them, after waiting for what the backend's stream still runs.  Waits for the copy:
+ * a set-up call. */
+int x3d_ibm_set_weights(x3d_ibm *ibm, const double *wx, const double *wy, const double *wz);
+/* x3d_ibm_body with the momentum it removes taken along: u, v, w get the bits of x3d_ibm_body (the same mapping, the same
+ * expression), and for c = u, v, w
+ *    I_c = sum over the valid points of the list of (((1 - ep1) f_c) wx[i]) (wy[j] wz[k]),
+ * f_c the value before the mask, every factor widened to double before any product.  Deterministic: a wave adds its segment
+ * in a fixed shuffle tree, a workgroup its four waves in wave order, workgroup g owns segments 4 g .. 4 g + 3 and leaves
+ * three FP64 partials in a buffer the mask owns (sized at x3d_ibm_create); a second launch of one workgroup adds the
+ * partials (thread t takes t, t + 256, ... ascending, then the same tree) and stores the sums into row_dev[0..2]
+ * (accumulate = 0) or adds them to what is there (accumulate != 0).  No floating-point atomics; partials and row are FP64
+ * in both flavours.  row_dev: device memory of the caller's, 3 doubles.  An empty list stores zeros with the second launch
+ * alone (accumulate = 0) or launches nothing.  Never waits for the host.  Without weights, with a null argument, another
+ * backend's mask, other dims than the mask's or u, v, w not three blocks: an error, nothing is launched. */
+int x3d_ibm_body_loads(x3d_backend *b, const x3d_ibm *ibm, x3d_real *u, x3d_real *v, x3d_real *w, const int dims[3],
+                       double *row_dev, int accumulate);
 /* compute_outflow_params, src/case/cylinder.f90:109-147, on one rank and without the host: a launch over the planes
  * i = 1, nx - 1, nx of u (FP64 partial sums in both flavours, fixed order, no atomics) and a one-workgroup finish leave
  *   params[0] = out_vel = max(u[nx-1]) * gdt / dx,   params[1] = flow_rate_diff = (sum u[1] - sum u[nx]) / (ny * nz)
@@ -903,6 +920,22 @@ int x3d_budget_profile_sums(x3d_backend *b, const x3d_budget_fields *f, const in
                             double *sums);
 /* prof[i] += (sums[i] * scale - prof[i]) * inc, i < n, in double: accumulate_mean on the plane means */
 int x3d_budget_profile_accumulate(x3d_backend *b, double *prof, const double *sums, long n, double scale, double inc);
+
+/* ---- point probes (csrc/probe.hip).  Not in the reference: this project's own addition.  A probe sits on a vertex; a sample
+ * is the value of u, v, w there, widened to double, in row_dev[3 slot + c] of a row of 3 n_total doubles. */
+#define X3D_PROBE_MAX 4096
+typedef struct x3d_probe x3d_probe;
+/* ijk_local[n_owned][3]: the 0-based LOCAL vertex indices of the probes this rank owns (inside the backend's vertex dims);
+ * slot_of[n_owned]: their slots in the row, each in [0, n_total) and owned once; 1 <= n_total <= X3D_PROBE_MAX;
+ * n_owned = 0 is allowed (both arrays may then be null).  Host arrays, read once. */
+int x3d_probe_create(x3d_backend *b, const int *ijk_local, int n_owned, const int *slot_of, int n_total, x3d_probe **out);
+/* one launch, one thread per (owned probe, field): row_dev[3 slot + c] = (double) f_c[i, j, k].  The slots of probes this
+ * rank does not own are not written.  Ordered on the backend's stream behind a queue of the deferred-execution layer, never
+ * waits for the host; no owned probe: no launch.  A null argument, another backend's probes, or a probe outside dims: an
+ * error, nothing is launched. */
+int x3d_probe_sample(x3d_backend *b, const x3d_probe *p, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                     const int dims[3], double *row_dev);
+int x3d_probe_destroy(x3d_probe *p);
 
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);

@@ -60,7 +60,10 @@ def make_cylinder(dims=(257, 128, 32), L=(20.0, 12.0, 6.0), Re=300.0, dt=0.0075,
     backend = HipBackend(mesh, device=device, lazy=lazy)
     solver = Solver(backend, mesh, SolverConfig(Re=Re, dt=dt, time_intg=time_intg, poisson_solver_type=poisson,
                                                  fused=fused, ibm_on=True))
-    if ep1 is None:
+    own_body = ep1 is None
+    if own_body:
         ep1 = cylinder_mask(mesh, (L[0] / 4.0, L[1] / 2.0) if centre is None else centre, radius, axis=2)
     solver.ibm = Ibm(solver, ep1)
+    if own_body:
+        solver.ibm.area_ref = 2.0 * float(radius) * float(L[2])  # D * L_z: the frontal area the loads' coefficients refer to
     return CylinderCase(solver, CylinderConfig(**cylinder_kw))

@@ -238,6 +238,8 @@ PROTOTYPES = {
     "x3d_ibm_destroy": (I, [VP]),
     "x3d_ibm_counts": (I, [VP, ctypes.POINTER(ctypes.c_long)]),
     "x3d_ibm_body": (I, [VP, VP, VP, VP, VP, c_int_p]),
+    "x3d_ibm_set_weights": (I, [VP] + [ctypes.POINTER(ctypes.c_double)] * 3),
+    "x3d_ibm_body_loads": (I, [VP, VP, VP, VP, VP, c_int_p, VP, I]),
     "x3d_outflow_params": (I, [VP, VP, c_int_p, D, D, ctypes.POINTER(VP)]),
     "x3d_outflow_params_get": (I, [VP, c_double_p]),
     "x3d_cylinder_apply_bc": (I, [VP, VP, VP, VP, VP, VP, VP, c_int_p, VP]),
@@ -261,6 +263,9 @@ PROTOTYPES = {
     "x3d_diag_max_sum": (I, [VP, VP, c_int_p, VP]),
     "x3d_budget_profile_sums": (I, [VP, VP, c_int_p, I, ctypes.c_double, VP]),
     "x3d_budget_profile_accumulate": (I, [VP, VP, VP, ctypes.c_long, ctypes.c_double, ctypes.c_double]),
+    "x3d_probe_create": (I, [VP, c_int_p, I, c_int_p, I, ctypes.POINTER(VP)]),
+    "x3d_probe_sample": (I, [VP, VP, VP, VP, VP, c_int_p, VP]),
+    "x3d_probe_destroy": (I, [VP]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),

@@ -1063,6 +1063,26 @@ class HipBackend:
         _lib.check(self.lib.x3d_inlet_noise(self.h, f.ptr, self._dims(VERT), float(base), float(amp),
                                             int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)))
 
+    def ibm_body_loads(self, ibm_h, u, v, w, row_ptr, accumulate):
+        """x3d_ibm_body with the impulse it removes taken along (csrc/ibm.hip): the sums over the work list go to (or, with
+        accumulate, are added to) the three doubles at the device address row_ptr.  No host synchronisation."""
+        for f in (u, v, w):
+            if f.dir != DIR_X:
+                raise X3dError("ibm_body_loads: DIR_X fields are needed")
+        _lib.check(self.lib.x3d_ibm_body_loads(self.h, ibm_h, u.ptr, v.ptr, w.ptr, self._dims(VERT),
+                                               VP(int(row_ptr)) if row_ptr else None, int(bool(accumulate))))
+
+    # ------------------------------------------------------------ point probes (csrc/probe.hip)
+    def probe_sample(self, probe_h, u, v, w, row_ptr):
+        """u, v, w at the owned probes, widened to double, into the row of 3 n doubles at the device address row_ptr: one
+        launch, no host synchronisation"""
+        for f in (u, v, w):
+            if f.dir != DIR_X:
+                raise X3dError("probe_sample: DIR_X fields are needed")
+        self._need_vert("probe_sample", u, v, w)
+        _lib.check(self.lib.x3d_probe_sample(self.h, probe_h, u.ptr, v.ptr, w.ptr, self._dims(VERT),
+                                             VP(int(row_ptr)) if row_ptr else None))
+
     # ------------------------------------------------------------ snapshots (csrc/snapshot.hip)
     SNAP_KINDS = {"copy": 0, "vort": 1, "qcrit": 2}
 

@@ -57,6 +57,11 @@ class BaseCase:
         # optional diagnostics.Diagnostics(solver, cfg, append=self.restarted): run() then samples, polls and finalises it
         self.diagnostics = None
         self.budgets = None  # optional budgets.Budgets(solver, cfg): run() then samples and writes it (not in the reference)
+        # optional loads.Loads(solver, cfg, append=self.restarted): Ibm.body then takes the force on the body along; run()
+        # polls and finalises it.  It reads no completed state: not one of `attached` below
+        self.loads = None
+        # optional probes.Probes(solver, cfg, append=self.restarted): run() then samples, polls and finalises it
+        self.probes = None
         self.restarted = False
         self.step_times = []
         self.initial_conditions()
@@ -187,7 +192,8 @@ class BaseCase:
             # a statistics, spectra or budgets sample, a row of the diagnostics series, a snapshot
             # (snapshot_manager.f90:125-126) and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step) read the
             # velocity like an output step does
-            attached = [a for a in (self.stats, self.spectra, diag, bud, snap, ckpt) if a is not None]
+            loads, probes = self.loads, self.probes
+            attached = [a for a in (self.stats, self.spectra, diag, bud, probes, snap, ckpt) if a is not None]
             read = (s.n_output > 0 and it % s.n_output == 0) or any(a.reads_state(it) for a in attached)
             snap_due = snap is not None and snap.reads_state(it)
             budgets_due = bud is not None and bud.pressure_due(it)  # (a budgets sample with pressure=True reads it too)
@@ -201,6 +207,8 @@ class BaseCase:
                 diag.update(it)  # nine gradients, one reduction into the device table; no host wait
             if bud is not None:
                 bud.update(it)  # nine gradients, the vertex pressure, one reduction, the recurrence; no host wait
+            if probes is not None:
+                probes.update(it)  # one gather into the device table; no host wait
             if s.n_output > 0 and it % s.n_output == 0:
                 row = self.postprocess(it, it * s.dt)
                 if verbose and s.mesh.is_root():
@@ -217,9 +225,15 @@ class BaseCase:
                 snap.poll()     # files of the snapshots whose copies have landed
             if diag is not None:
                 diag.poll()     # rows of the tables whose copies have landed
+            if loads is not None:
+                loads.poll()
+            if probes is not None:
+                probes.poll()
             if ckpt is not None:
-                if diag is not None and ckpt.cfg.due(it):
-                    diag.flush()  # the series on disk reaches the checkpoint it may be continued from
+                if ckpt.cfg.due(it):
+                    for series in (diag, loads, probes):
+                        if series is not None:
+                            series.flush()  # the series on disk reaches the checkpoint it may be continued from
                 ckpt.write(it)  # one pack launch, one asynchronous copy; no host wait
                 ckpt.poll()     # the file of a checkpoint whose copy has landed
             s.backend.sync()
@@ -231,6 +245,10 @@ class BaseCase:
             self.checkpoints.finalise()
         if self.diagnostics is not None:
             self.diagnostics.finalise()
+        if self.loads is not None:
+            self.loads.finalise()
+        if self.probes is not None:
+            self.probes.finalise()
         return self.monitoring.rows
 
 

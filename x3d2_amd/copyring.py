@@ -7,8 +7,9 @@ once it is done, never waiting; by drain() and land(), which wait for it.  The (
 landed waits for it, lands it, and counts `waits`.
 
 The copies of one backend share one in-order stream, so an older copy that is not done implies a newer one that is not:
-everything here goes oldest first.  The library keys its copy events by device pointer and has 8 per backend
-(X3D_SNAP_SLOTS): a slot is reallocated only when a larger size is asked for, and never while its copy is unlanded."""
+everything here goes oldest first.  The library keys its copy events by device pointer and has 16 per backend
+(X3D_SNAP_SLOTS): a slot is reallocated only when a larger size is asked for, and never while its copy is unlanded.  The
+rings of one backend together: Snapshots 2, Checkpoints 1, Diagnostics, Loads and Probes 2 each -- 9 with all attached."""
 from .common import X3dError
 
 

@@ -21,6 +21,8 @@ struct x3d_ibm {
     long nseg, nmasked;
     int4 *seg;     // device [nseg]: (i0, j, k, valid points) of a segment, 0-based, i0 a multiple of 64; ascending in (k, j, i0)
     real_t *mask;  // device [nseg][64]: the mask values of the listed segments (1.0 beyond the row's end)
+    double *part;  // device [(nseg + 3) / 4][3]: the workgroups' partial impulses of x3d_ibm_body_loads
+    double *wgt;   // device [nx + ny + nz]: the quadrature weights w_x, w_y, w_z (x3d_ibm_set_weights), null until set
 };
 
 extern "C" int x3d_ibm_create(x3d_backend *b, const real_t *ep1_host, const int dims[3], x3d_ibm **out)
@@ -53,15 +55,19 @@ extern "C" int x3d_ibm_create(x3d_backend *b, const real_t *ep1_host, const int 
     m->nmasked = nmasked;
     m->seg = nullptr;
     m->mask = nullptr;
+    m->part = nullptr;
+    m->wgt = nullptr;
     if (m->nseg > 0) {
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->seg), sizeof(int4) * seg.size());
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->mask), sizeof(real_t) * mask.size());
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->part), sizeof(double) * 3 * ((seg.size() + 3) / 4));
         // (the host vectors die with this call: synchronous copies)
         if (e == hipSuccess) e = hipMemcpy(m->seg, seg.data(), sizeof(int4) * seg.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(m->mask, mask.data(), sizeof(real_t) * mask.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             if (m->seg) hipFree(m->seg);
             if (m->mask) hipFree(m->mask);
+            if (m->part) hipFree(m->part);
             delete m;
             x3d_set_error("x3d_ibm_create: %s", hipGetErrorString(e));
             return 1;
@@ -77,6 +83,8 @@ extern "C" int x3d_ibm_destroy(x3d_ibm *m)
     if (!m) return 0;
     if (m->seg) hipFree(m->seg);
     if (m->mask) hipFree(m->mask);
+    if (m->part) hipFree(m->part);
+    if (m->wgt) hipFree(m->wgt);
     delete m;
     return 0;
 }
@@ -125,6 +133,125 @@ extern "C" int x3d_ibm_body(x3d_backend *b, const x3d_ibm *m, real_t *u, real_t 
     ProfScope ps(b, X3D_K_BLAS1);
     hipLaunchKernelGGL(k_ibm_body, dim3((unsigned)((m->nseg + 3) / 4)), dim3(256), 0, b->stream, u, v, w,
                        (const int4 *)m->seg, (const real_t *)m->mask, m->nseg, (long)b->nxp, (long)b->nyp);
+    X3D_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------- loads: the momentum the mask removes
+extern "C" int x3d_ibm_set_weights(x3d_ibm *m, const double *wx, const double *wy, const double *wz)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(m && wx && wy && wz, "x3d_ibm_set_weights: null argument");
+    const size_t n = (size_t)m->nx + m->ny + m->nz;
+    std::vector<double> host(n);
+    std::copy(wx, wx + m->nx, host.begin());
+    std::copy(wy, wy + m->ny, host.begin() + m->nx);
+    std::copy(wz, wz + m->nz, host.begin() + m->nx + m->ny);
+    if (!m->wgt) X3D_HIP(hipMalloc(reinterpret_cast<void **>(&m->wgt), sizeof(double) * n));
+    else X3D_HIP(hipStreamSynchronize(m->b->stream));  // (a launch that reads the table being replaced may still run)
+    // (the host vector dies with this call: a synchronous copy)
+    X3D_HIP(hipMemcpy(m->wgt, host.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// k_ibm_body's mapping and its expression for u, v, w (the same bits), and on the way the three impulses of the segment:
+// term_c = (((1 - m) f_c) w_x[i]) (w_y[j] w_z[k]), every factor a double before any product.  A wave adds its 64 terms in a
+// fixed shuffle tree (lanes beyond the row's end and waves beyond the list hold zeros), the workgroup's four waves are added
+// in wave order, and workgroup g leaves the impulses of segments 4 g .. 4 g + 3 in part[g][0..2].  No atomics.
+__global__ void __launch_bounds__(256) k_ibm_body_loads(real_t *__restrict__ u, real_t *__restrict__ v, real_t *__restrict__ w,
+                                                        const int4 *__restrict__ seg, const real_t *__restrict__ mask, long nseg,
+                                                        long nxp, long nyp, const double *__restrict__ wx,
+                                                        const double *__restrict__ wy, const double *__restrict__ wz,
+                                                        double *__restrict__ part)
+{
+    __shared__ double sm[4][3];
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long s = wv + 4L * blockIdx.x;
+    const int ln = threadIdx.x & 63;
+    double tu = 0.0, tv = 0.0, tw = 0.0;
+    if (s < nseg) {
+        const int4 e = seg[s];
+        if (ln < e.w) {  // beyond the row's end: padding, or the next row -- never read, never written
+            const real_t m = __builtin_nontemporal_load(mask + s * 64 + ln);
+            const long off = nxp * (e.y + nyp * (long)e.z) + e.x + ln;
+            const real_t fu = u[off], fv = v[off], fw = w[off];
+            const double a = 1.0 - (double)m, wi = wx[e.x + ln], wjk = wy[e.y] * wz[e.z];
+            tu = ((a * (double)fu) * wi) * wjk;
+            tv = ((a * (double)fv) * wi) * wjk;
+            tw = ((a * (double)fw) * wi) * wjk;
+            u[off] = fu * m;
+            v[off] = fv * m;
+            w[off] = fw * m;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        tu += __shfl_down(tu, o);
+        tv += __shfl_down(tv, o);
+        tw += __shfl_down(tw, o);
+    }
+    if (ln == 0) { sm[wv][0] = tu; sm[wv][1] = tv; sm[wv][2] = tw; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        part[3 * (long)blockIdx.x + threadIdx.x] =
+            ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+}
+
+// One workgroup: thread t adds the partials t, t + 256, ... in ascending order, then the same shuffle tree and wave order as
+// above -- an order fixed by nparts alone.  row[0..2] = the sums (accumulate = 0) or row[0..2] + the sums (accumulate = 1).
+__global__ void __launch_bounds__(256) k_ibm_loads_finish(const double *__restrict__ part, long nparts, double *__restrict__ row,
+                                                          int accumulate)
+{
+    __shared__ double sm[4][3];
+    double tu = 0.0, tv = 0.0, tw = 0.0;
+    for (long p = threadIdx.x; p < nparts; p += 256) {
+        tu += part[3 * p + 0];
+        tv += part[3 * p + 1];
+        tw += part[3 * p + 2];
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        tu += __shfl_down(tu, o);
+        tv += __shfl_down(tv, o);
+        tw += __shfl_down(tw, o);
+    }
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    if (ln == 0) { sm[wv][0] = tu; sm[wv][1] = tv; sm[wv][2] = tw; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const double t = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+        row[threadIdx.x] = accumulate ? row[threadIdx.x] + t : t;
+    }
+}
+
+extern "C" int x3d_ibm_body_loads(x3d_backend *b, const x3d_ibm *m, real_t *u, real_t *v, real_t *w, const int dims[3],
+                                  double *row_dev, int accumulate)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(b && m && u && v && w && dims && row_dev, "x3d_ibm_body_loads: null argument");
+    X3D_REQUIRE(m->b == b, "x3d_ibm_body_loads: the mask belongs to another backend");
+    X3D_REQUIRE(dims[0] == m->nx && dims[1] == m->ny && dims[2] == m->nz,
+                "x3d_ibm_body_loads: dims (%d,%d,%d) are not the mask's (%d,%d,%d)", dims[0], dims[1], dims[2], m->nx, m->ny,
+                m->nz);
+    X3D_REQUIRE(u != v && u != w && v != w, "x3d_ibm_body_loads: u, v, w must be three blocks");
+    X3D_REQUIRE(m->wgt, "x3d_ibm_body_loads: x3d_ibm_set_weights has not been called on this mask");
+    if (m->nseg == 0 && accumulate) return 0;  // a mask of ones adds zeros: nothing to launch
+    if (m->nseg > 0) {
+        X3D_LAZY_OUT(b, u, false);
+        X3D_LAZY_OUT(b, v, false);
+        X3D_LAZY_OUT(b, w, false);
+    }
+    X3D_LAZY_EAGER(b);
+    const long nparts = (m->nseg + 3) / 4;
+    if (nparts > 0) {  // (timed as x3d_ibm_body's launch is; the finishing launch counts as a reduction)
+        ProfScope ps(b, X3D_K_BLAS1);
+        hipLaunchKernelGGL(k_ibm_body_loads, dim3((unsigned)nparts), dim3(256), 0, b->stream, u, v, w, (const int4 *)m->seg,
+                           (const real_t *)m->mask, m->nseg, (long)b->nxp, (long)b->nyp, (const double *)m->wgt,
+                           (const double *)(m->wgt + m->nx), (const double *)(m->wgt + m->nx + m->ny), m->part);
+    }
+    {
+        ProfScope ps(b, X3D_K_REDUCE);
+        hipLaunchKernelGGL(k_ibm_loads_finish, dim3(1), dim3(256), 0, b->stream, (const double *)m->part, nparts, row_dev,
+                           accumulate ? 1 : 0);
+    }
     X3D_HIP(hipGetLastError());
     return 0;
 }

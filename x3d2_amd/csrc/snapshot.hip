@@ -90,7 +90,10 @@ __global__ void __launch_bounds__(256) k_snapshot_pack(SnapTab T, SnapGeom G, OU
 // ---------------------------------------------------------------- copies in flight
 // One slot per packed device buffer: ev_pack orders the copy behind the pack, ev_done is recorded behind the copy and is
 // what x3d_snapshot_done / _wait look at -- and what the NEXT pack into the same buffer waits for, on the device.
-#define X3D_SNAP_SLOTS 8
+// Who holds packed buffers on one backend (copyring.CopyRing slots): Snapshots 2, Checkpoints 1, and 2 for each series --
+// Diagnostics, Loads, Probes: 9 with everything attached.  A ring slot that grows takes a new buffer and with it a new slot
+// here, so the limit leaves room for that.
+#define X3D_SNAP_SLOTS 16
 struct SnapSlot {
     void *dev;
     hipEvent_t ev_pack, ev_done;

@@ -171,20 +171,128 @@ def trim_csv(path, t_last, columns):
     return n
 
 
+# ---------------------------------------------------------------- a series: tables, ring, file
+class Series:
+    """the table -> pinned copy -> file path of a series (module docstring, "Tables" and "File") for rows of `width` doubles
+    that kernels of the owner's write into the device table: row_address(it) is where the next row goes, commit() closes
+    it.  combine(raw) joins a landed table over the ranks (here: ONE sum over all slots); values(raw) -> the columns of a
+    row; comments: lines behind the header.  Diagnostics below, loads.Loads and probes.Probes are such series."""
+
+    def __init__(self, solver, who, prefix, flush_every, width, columns, append, comments=()):
+        self.solver, self.width, self.columns = solver, int(width), tuple(columns)
+        b, m = solver.backend, solver.mesh
+        if flush_every > MAX_FLUSH_EVERY:
+            raise X3dError("%s: flush_every = %d, a device table holds at most %d rows" % (who, flush_every, MAX_FLUSH_EVERY))
+        self.flush_every = int(flush_every)
+        self.sample_count = 0
+        self.ring = CopyRing(b, 2, self._land)  # (an attached but idle series takes nothing)
+        self._slot = None     # the ring slot of the current table, acquired by the first row of a batch
+        self._meta = np.zeros((self.flush_every, 2), dtype=np.float64)  # (iteration, time) of the current table's rows
+        self._count = 0
+        self._rows = []  # (iteration, time, the combined raw row)
+        self.file = prefix + ".csv" if m.is_root() else None
+        if self.file is not None:
+            if append and os.path.exists(self.file):
+                trim_csv(self.file, int(solver.current_iter) * float(solver.dt), self.columns)
+            else:
+                with open(self.file, "w") as fh:
+                    fh.write(format_header(self.columns))
+                    fh.writelines(comments)
+
+    @property
+    def sync_count(self):
+        """how often a row had to wait for a table whose copy had not been landed"""
+        return self.ring.waits
+
+    def row_address(self, it):
+        """the device address of the row of iteration `it` in the current table (a third table before the first has
+        landed waits here)"""
+        if self._slot is None:  # (asked once per kernel that writes the row: the first call of a table acquires it)
+            self._slot = self.ring.acquire(self.flush_every * self.width * 8)
+        self._meta[self._count] = (int(it), int(it) * float(self.solver.dt))
+        return self._slot.dev.data_ptr() + self._count * self.width * 8
+
+    def commit(self):
+        self._count += 1
+        self.sample_count += 1
+        if self._count == self.flush_every:
+            self.flush()
+
+    def flush(self):
+        """start the copy of the current table's rows (if it has any) and go on with the other table; no host wait"""
+        if self._count == 0:
+            return False
+        n = self._count
+        self.ring.submit(self._slot, n * self.width * 8, [n, self._meta[:n].copy(), 0])  # (rows, meta, polls seen)
+        self._slot, self._count = None, 0
+        return True
+
+    def _land(self, payload, raw):
+        b = self.solver.backend
+        n, meta, _ = payload
+        raw = raw.view(np.float64).reshape(n, self.width).copy()
+        if b.comm.size > 1:
+            self.combine(raw)
+        lines = []
+        for r in range(n):
+            self._rows.append((int(meta[r, 0]), float(meta[r, 1]), raw[r]))
+            lines.append(format_row(meta[r, 1], self.values(raw[r])))
+        if self.file is not None:
+            with open(self.file, "a") as fh:
+                fh.writelines(lines)
+        return n
+
+    def combine(self, raw):
+        """a landed table [rows, width] of this rank -> that of all ranks, in place; every rank calls it for the same table"""
+        sums = torch.from_numpy(raw)  # (shares raw's memory)
+        self.solver.backend.comm.allreduce_tensor(sums, "sum")
+
+    def poll(self):
+        """turn the tables whose copies have landed into rows, oldest first; returns the rows added.  One rank: never
+        blocks.  Several ranks: a table is landed by the second poll after its flush, so that the collectives match."""
+        if self.solver.backend.comm.size == 1:
+            return sum(self.ring.poll())
+        n = 0
+        for slot, p in self.ring.pending():
+            p[2] += 1
+            if p[2] < 2:
+                break
+            n += self.ring.land(slot)
+        return n
+
+    def finalise(self):
+        """flush, then wait for and write what is left"""
+        self.flush()
+        return sum(self.ring.drain())
+
+    def values(self, raw):
+        return list(raw)
+
+    def raw_rows(self):
+        """[nrows, width]: the raw slots of the rows landed so far (summed over the ranks)"""
+        return np.array([r[2] for r in self._rows], dtype=np.float64).reshape(len(self._rows), self.width)
+
+    def rows(self):
+        """the rows landed so far as a structured array: iteration, time and the columns"""
+        dt = [("iteration", np.int64), ("time", np.float64)] + [(c, np.float64) for c in self.columns]
+        out = np.zeros(len(self._rows), dtype=dt)
+        for i, (it, t, raw) in enumerate(self._rows):
+            out[i] = (it, t) + tuple(self.values(raw))
+        return out
+
+
 # ---------------------------------------------------------------- the device object
-class Diagnostics:
+class Diagnostics(Series):
     """Diagnostics(solver, cfg, append=False), attached as `case.diagnostics = Diagnostics(case.solver, cfg)`:
     BaseCase.run then calls update(it) and poll() once per step, flush() before a checkpoint and finalise() at the end.
     A restarted run constructs it with append=case.restarted."""
 
     def __init__(self, solver, cfg, append=False):
-        self.solver, self.cfg = solver, cfg
+        self.cfg = cfg
         b, m = solver.backend, solver.mesh
-        if cfg.flush_every > MAX_FLUSH_EVERY:
-            raise X3dError("Diagnostics: flush_every = %d, a device table holds at most %d rows"
-                           % (cfg.flush_every, MAX_FLUSH_EVERY))
         self.y_walls = not bool(m.periodic_BC[1])
-        self.columns = column_names(cfg.divergence, self.y_walls)
+        super().__init__(solver, "Diagnostics", cfg.prefix, cfg.flush_every, NSLOT, column_names(cfg.divergence, self.y_walls),
+                         append)
         gv, gc = m.get_global_dims(VERT), m.get_global_dims(CELL)
         self.n_vert, self.n_cell = float(np.prod(gv)), float(np.prod(gc))
         self.n_plane = float(int(gv[0]) * int(gv[2]))
@@ -192,25 +300,7 @@ class Diagnostics:
         self.last_y = self.y_walls and int(m.nrank_dir[1]) == int(m.nproc_dir[1]) - 1
         self.ih_host = spacing_tables(m)
         self.ih = [torch.from_numpy(a).to(b.device) for a in self.ih_host]
-        self.sample_count = 0
-        self.ring = CopyRing(b, 2, self._land)  # (an attached but idle Diagnostics takes nothing)
-        self._slot = None     # the ring slot of the current table, acquired by the first row of a batch
         self._scratch = None
-        self._meta = np.zeros((cfg.flush_every, 2), dtype=np.float64)  # (iteration, time) of the current table's rows
-        self._count = 0       # rows in the current table
-        self._rows = []       # (iteration, time, the combined raw row)
-        self.file = cfg.prefix + ".csv" if m.is_root() else None
-        if self.file is not None:
-            if append and os.path.exists(self.file):
-                trim_csv(self.file, int(solver.current_iter) * float(solver.dt), self.columns)
-            else:
-                with open(self.file, "w") as fh:
-                    fh.write(format_header(self.columns))
-
-    @property
-    def sync_count(self):
-        """how often a row had to wait for a table whose copy had not been landed"""
-        return self.ring.waits
 
     # ------------------------------------------------------------ taking a sample
     def reduce(self, u, v, w, grads, out=None):
@@ -231,17 +321,12 @@ class Diagnostics:
         """one row for iteration `it` into the current device table from fields of the caller's: the reduction over u, v,
         w and the nine gradients and, if div_u is given, the max / sum of that block; no host wait unless both tables
         are in flight"""
-        if self._count == 0:  # (a third table before the first has landed waits here)
-            self._slot = self.ring.acquire(self.cfg.flush_every * NSLOT * 8)
+        self.row_address(it)  # (a third table before the first has landed waits here)
         row = self._slot.dev.view(torch.float64)[self._count * NSLOT:(self._count + 1) * NSLOT]
         self.reduce(u, v, w, grads, out=row)
         if div_u is not None:
             self.solver.backend.diag_max_sum(div_u, row.data_ptr())
-        self._meta[self._count] = (int(it), int(it) * float(self.solver.dt))
-        self._count += 1
-        self.sample_count += 1
-        if self._count == self.cfg.flush_every:
-            self.flush()
+        self.commit()
 
     def sample(self, it):
         """one row for iteration `it` from the solver's velocity: nine gradients, the reduction, the divergence"""
@@ -270,66 +355,15 @@ class Diagnostics:
         self.sample(it)
         return True
 
-    # ------------------------------------------------------------ moving the tables
-    def flush(self):
-        """start the copy of the current table's rows (if it has any) and go on with the other table; no host wait"""
-        if self._count == 0:
-            return False
-        n = self._count
-        self.ring.submit(self._slot, n * NSLOT * 8, [n, self._meta[:n].copy(), 0])  # (rows, meta, polls seen)
-        self._count = 0
-        return True
+    # ------------------------------------------------------------ several ranks, columns
+    def combine(self, raw):
+        """two collectives: the sum over slots 0-7, the maximum over slots 8-13"""
+        comm = self.solver.backend.comm
+        sums, maxs = torch.from_numpy(raw[:, SUM_SLOTS].copy()), torch.from_numpy(raw[:, MAX_SLOTS].copy())
+        comm.allreduce_tensor(sums, "sum")
+        comm.allreduce_tensor(maxs, "max")
+        raw[:, SUM_SLOTS], raw[:, MAX_SLOTS] = sums.numpy(), maxs.numpy()
 
-    def _land(self, payload, raw):
-        """the ring's landing: a table's bytes -> rows and lines; returns the rows added"""
-        b = self.solver.backend
-        n, meta, _ = payload
-        raw = raw.view(np.float64).reshape(n, NSLOT).copy()
-        if b.comm.size > 1:
-            sums, maxs = torch.from_numpy(raw[:, SUM_SLOTS].copy()), torch.from_numpy(raw[:, MAX_SLOTS].copy())
-            b.comm.allreduce_tensor(sums, "sum")
-            b.comm.allreduce_tensor(maxs, "max")
-            raw[:, SUM_SLOTS], raw[:, MAX_SLOTS] = sums.numpy(), maxs.numpy()
-        lines = []
-        for r in range(n):
-            self._rows.append((int(meta[r, 0]), float(meta[r, 1]), raw[r]))
-            lines.append(format_row(meta[r, 1], self._derive(raw[r])))
-        if self.file is not None:
-            with open(self.file, "a") as fh:  # (closed per batch: what scalar_series_t's flush gives)
-                fh.writelines(lines)
-        return n
-
-    def poll(self):
-        """turn the tables whose copies have landed into rows, oldest first; returns the rows added.  One rank: never
-        blocks.  Several ranks: a table is landed by the second poll after its flush (see the module docstring)."""
-        if self.solver.backend.comm.size == 1:
-            return sum(self.ring.poll())
-        n = 0
-        for slot, p in self.ring.pending():
-            p[2] += 1
-            if p[2] < 2:
-                break
-            n += self.ring.land(slot)
-        return n
-
-    def finalise(self):
-        """flush, then wait for and write what is left"""
-        self.flush()
-        return sum(self.ring.drain())
-
-    # ------------------------------------------------------------ results
-    def _derive(self, raw):
+    def values(self, raw):
         s = self.solver
         return derive(raw, self.n_vert, self.n_cell, self.n_plane, float(s.nu), float(s.dt), self.cfg.divergence, self.y_walls)
-
-    def raw_rows(self):
-        """[nrows, 16]: the raw slots of the rows landed so far (combined over the ranks)"""
-        return np.array([r[2] for r in self._rows], dtype=np.float64).reshape(len(self._rows), NSLOT)
-
-    def rows(self):
-        """the rows landed so far as a structured array: iteration, time and the columns"""
-        dt = [("iteration", np.int64), ("time", np.float64)] + [(c, np.float64) for c in self.columns]
-        out = np.zeros(len(self._rows), dtype=dt)
-        for i, (it, t, raw) in enumerate(self._rows):
-            out[i] = (it, t) + tuple(self._derive(raw))
-        return out

@@ -60,6 +60,8 @@ class Ibm:
         self.h = None          # the library's work list (sparse form)
         self.ep1_field = None  # the reference's device mask block (X3D_NO_IBM_SPARSE=1)
         self.n_segments = self.n_masked = 0
+        self.loads = None      # optional loads.Loads: `body` then takes the impulse it removes along on the steps that are due
+        self.area_ref = None   # the reference area of the body's force coefficients, if whoever made the mask knows one
         b = self.backend
         nx, ny, nz = b.mesh.get_dims(VERT)
         self.ep1 = np.ascontiguousarray(ep1, dtype=np.float64)
@@ -102,7 +104,12 @@ class Ibm:
             for f in (u, v, w):
                 if f.dir != DIR_X:
                     raise X3dError("Ibm.body: DIR_X fields are needed")
-            _lib.check(b.lib.x3d_ibm_body(b.h, self.h, u.ptr, v.ptr, w.ptr, b._dims(VERT)))
+            row = self.loads.begin_body() if self.loads is not None else None
+            if row is None:
+                _lib.check(b.lib.x3d_ibm_body(b.h, self.h, u.ptr, v.ptr, w.ptr, b._dims(VERT)))
+            else:
+                b.ibm_body_loads(self.h, u, v, w, row[0], row[1])
+                self.loads.end_body()
         else:
             b.vecmult(u, self.ep1_field)
             b.vecmult(v, self.ep1_field)
