@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -63,6 +63,13 @@ without, and (d) the same with Loads and Probes: wall time, the host waits (x3d_
 steps and in finalise, and the launch groups of the per-class timers per sub-step (taken in a second, untimed run of 5 steps;
 with Loads they grow by exactly one, the finishing launch).  No gate on the times; the two counts are gates.  The lines are
 appended to profiles/loads.jsonl.
+
+Family "les" (--snap-n^3 = 512^3, median of --stat-iters with the quartiles as spread; not part of "all"): (a) x3d_les_stress,
+both launches (HIP events), for both models, in TB/s on the 128 B/DoF it reads and writes in FP64 (the nine gradients are
+restored before every timed call: the kernel works in place), next to the fused statistics update (168 B/DoF, also a read +
+write stream) in the same process, and the gate t_stress <= 1.25 (128 / 168) t_stats_update; (b) a whole Les.add next to a
+whole Diagnostics sample, wall clock around a device sync; (c) 20 fused RK3 TGV steps with and without the model: added wall
+time per step (no gate).  The lines are appended to profiles/les.jsonl.
 """
 import argparse
 import json
@@ -871,13 +878,120 @@ def bench_loads(args):
           "passed": bool(res["loads"]["launch_groups_per_substep"] - base["launch_groups_per_substep"] == 1.0)})
 
 
+def bench_les(args):
+    """one JSON line per measurement of the "les" family, printed and appended to profiles/les.jsonl"""
+    import ctypes
+    import tempfile
+
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.common import DIR_X, VERT
+    from x3d2_amd.diagnostics import Diagnostics, DiagnosticsConfig
+    from x3d2_amd.les import Les, LesConfig
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    tmp = tempfile.mkdtemp(prefix="x3d_les_")
+    out_path = os.path.join(ROOT, "profiles", "les.jsonl")
+
+    def emit(row):
+        row = dict({"family": "les", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    case = make_tgv(n, fused=True)
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    case.step(1)
+    s.flush_grad()
+    # (a) the kernel alone; it overwrites its input, so the gradients are copied back (untimed) before every call
+    grads = s.velocity_gradients()
+    saved = [al.get_block(DIR_X, VERT) for _ in range(9)]
+    for d, g in zip(saved, grads):
+        b.veccopy(d, g)
+    t_stress = {}
+    for model in ("smagorinsky", "wale"):
+        les = Les(s, LesConfig(model=model))
+        ms, times = ctypes.c_float(), []
+        for i in range(args.stat_warmup + args.stat_iters):
+            for d, g in zip(saved, grads):
+                b.veccopy(g, d)
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            les.stress(grads)
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times.append(ms.value)
+        t = spread(times)
+        t_stress[model] = t["ms_median"]
+        nbytes = 16 * rb * n ** 3
+        emit(dict({"op": "x3d_les_stress, %s: both launches (9 blocks read, 7 written)" % model, "bytes_per_dof": 16 * rb,
+                   "TBs": nbytes / t["ms_median"] / 1e9, "ceiling": nbytes / t["ms_median"] / 1e6 / 6200.0,
+                   "row_pitch": b.padded_dims[0], "monitor": les.monitor()}, **t))
+    for g in grads:
+        al.release_block(g)
+    for f in saved:  # (the nine accumulators of the statistics update)
+        f.fill(0.0)
+    t = spread(timed_events(args, b, lambda: b.stats_update_uvw(s.u, s.v, s.w, saved, 0.125)))
+    nbytes = 21 * rb * n ** 3
+    emit(dict({"op": "x3d_stats_update_uvw on the same box (3 blocks read, 9 read and written)", "bytes_per_dof": 21 * rb,
+               "TBs": nbytes / t["ms_median"] / 1e9, "ceiling": nbytes / t["ms_median"] / 1e6 / 6200.0}, **t))
+    for f in saved:
+        al.release_block(f)
+    for model in ("smagorinsky", "wale"):
+        limit = 1.25 * (128.0 / 168.0) * t["ms_median"]
+        emit({"op": "gate: t_stress <= 1.25 (128 / 168) t_stats_update, %s" % model, "stress_ms_median": t_stress[model],
+              "stats_update_ms_median": t["ms_median"], "limit_ms": limit, "passed": bool(t_stress[model] <= limit)})
+    # (b) a whole Les.add next to a whole Diagnostics sample: wall clock around a device sync, same state, same process
+    d = [al.get_block(DIR_X, VERT) for _ in range(3)]
+    for f in d:
+        f.fill(0.0)
+    for model in ("smagorinsky", "wale"):
+        les = Les(s, LesConfig(model=model))
+        s0 = b.sync_count()
+        t = spread(timed_wall(args, b, lambda: les.add(*d)))
+        emit(dict({"op": "Les.add, %s: 9 gradients + stress + 9 accumulated derivatives (wall clock)" % model,
+                   "stream_syncs_per_call": (b.sync_count() - s0) / float(args.stat_warmup + args.stat_iters)}, **t))
+    for f in d:
+        al.release_block(f)
+    dg = Diagnostics(s, DiagnosticsConfig(prefix=os.path.join(tmp, "a")))
+    count = [0]
+
+    def sample():
+        count[0] += 1
+        dg.sample(count[0])
+        dg.poll()
+
+    t = spread(timed_wall(args, b, sample))
+    emit(dict({"op": "Diagnostics sample: 9 gradients + reduction + divergence + max / sum (wall clock)"}, **t))
+    dg.finalise()
+    del case, s, b, al, dg, les, grads, saved, d
+    torch.cuda.empty_cache()
+    # (c) 20 steps with the model against the same run without (the parent's path)
+    res = {}
+    for model in (None, "smagorinsky", "wale"):
+        case = make_tgv(n, fused=True)
+        if model is not None:
+            case.solver.les = Les(case.solver, LesConfig(model=model))
+        case.run(n_iters=3)
+        case.solver.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        case.solver.backend.sync()
+        res[model] = (time.perf_counter() - t0) * 1e3
+        del case
+        torch.cuda.empty_cache()
+    for model in ("smagorinsky", "wale"):
+        emit({"op": "TGV, fused, RK3: 20 steps, %s" % model, "wall_ms_without": res[None], "wall_ms_with": res[model],
+              "ms_per_step_without": res[None] / 20.0, "added_ms_per_step": (res[model] - res[None]) / 20.0})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "loads",
-                                                               "budgets"))
+                                                               "budgets", "les"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -898,7 +1012,9 @@ def main():
         bench_budgets(args)
     if args.family == "loads":
         bench_loads(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads"):
+    if args.family == "les":
+        bench_les(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les"):
         return
     import torch
     from x3d2_amd import Mesh

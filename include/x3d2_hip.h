@@ -921,6 +921,32 @@ int x3d_budget_profile_sums(x3d_backend *b, const x3d_budget_fields *f, const in
 /* prof[i] += (sums[i] * scale - prof[i]) * inc, i < n, in double: accumulate_mean on the plane means */
 int x3d_budget_profile_accumulate(x3d_backend *b, double *prof, const double *sums, long n, double scale, double inc);
 
+/* ---- explicit LES on the device (csrc/les.hip): eddy viscosity and subgrid stress from the nine velocity gradients.  Not in
+ * the reference: this project's own addition.  With g_ij = grads[3 i + j], S_ij = 1/2 (g_ij + g_ji) and
+ * D2 = a_x[i] a_y[j] a_z[k] (the filter width squared; the tables hold h^(2/3)):
+ *    X3D_LES_SMAGORINSKY   nu_t = c2 D2 sqrt(2 S:S)
+ *    X3D_LES_WALE          G = g g, Sd_ij = 1/2 (G_ij + G_ji) - 1/3 delta_ij G_kk,
+ *                          nu_t = c2 D2 (Sd:Sd)^(3/2) / ((S:S)^(5/2) + (Sd:Sd)^(5/4)), 0 where the denominator is 0
+ * evaluated in double in BOTH flavours (products and sqrt only), each output rounded once to x3d_real.  One launch reads the
+ * nine blocks once and overwrites seven of them with tau_ij = 2 nu_t S_ij and nu_t:
+ *    tau_11 -> grads[0], tau_12 -> grads[1], tau_13 -> grads[2], nu_t -> grads[3], tau_22 -> grads[4], tau_23 -> grads[5],
+ *    tau_33 -> grads[8];  grads[6] and grads[7] keep what they hold
+ * over the dims interior (row padding is never read into a result and never written).  The same launch forms the row
+ *    0  sum nu_t      1  sum 2 nu_t S:S      2  max nu_t      3  max nu_t (ih_x[i]^2 + ih_y[j]^2 + ih_z[k]^2)
+ * (4 doubles in both flavours), deterministically, as the diagnostics row is formed: per-workgroup partials in a fixed order in
+ * the backend's reduction buffer, added in index order by a second small launch; no floating-point atomics; the launch
+ * geometry depends on dims alone.  Ordered on the backend's stream, no host wait, a queue of the deferred-execution layer
+ * runs first.  A bad argument (a null pointer, two gradient blocks that are one, non-positive dims, an unknown model, a
+ * negative c2, more partials than the reduction buffer holds) is an error and launches nothing. */
+enum { X3D_LES_SMAGORINSKY = 0, X3D_LES_WALE = 1 };
+typedef struct x3d_les_params {
+    int model;                        /* X3D_LES_* */
+    double c2;                        /* the model constant squared: C_s^2 or C_w^2 */
+    const double *a_x, *a_y, *a_z;    /* device tables of h^(2/3), dims[0], dims[1], dims[2] values */
+    const double *ih_x, *ih_y, *ih_z; /* device tables of inverse spacings, as x3d_diag_params' */
+} x3d_les_params;
+int x3d_les_stress(x3d_backend *b, x3d_real *const grads[9], const int dims[3], const x3d_les_params *params, double *row_dev);
+
 /* ---- point probes (csrc/probe.hip).  Not in the reference: this project's own addition.  A probe sits on a vertex; a sample
  * is the value of u, v, w there, widened to double, in row_dev[3 slot + c] of a row of 3 n_total doubles. */
 #define X3D_PROBE_MAX 4096

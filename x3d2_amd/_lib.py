@@ -263,6 +263,7 @@ PROTOTYPES = {
     "x3d_diag_max_sum": (I, [VP, VP, c_int_p, VP]),
     "x3d_budget_profile_sums": (I, [VP, VP, c_int_p, I, ctypes.c_double, VP]),
     "x3d_budget_profile_accumulate": (I, [VP, VP, VP, ctypes.c_long, ctypes.c_double, ctypes.c_double]),
+    "x3d_les_stress": (I, [VP, ctypes.POINTER(VP), c_int_p, VP, VP]),
     "x3d_probe_create": (I, [VP, c_int_p, I, c_int_p, I, ctypes.POINTER(VP)]),
     "x3d_probe_sample": (I, [VP, VP, VP, VP, VP, c_int_p, VP]),
     "x3d_probe_destroy": (I, [VP]),
@@ -284,6 +285,12 @@ class SnapshotVar(ctypes.Structure):
 class DiagParams(ctypes.Structure):
     """x3d_diag_params of include/x3d2_hip.h"""
     _fields_ = [("ih_x", VP), ("ih_y", VP), ("ih_z", VP), ("first_y", I), ("last_y", I)]
+
+
+class LesParams(ctypes.Structure):
+    """x3d_les_params of include/x3d2_hip.h"""
+    _fields_ = [("model", I), ("c2", ctypes.c_double), ("a_x", VP), ("a_y", VP), ("a_z", VP), ("ih_x", VP), ("ih_y", VP),
+                ("ih_z", VP)]
 
 
 class BudgetFields(ctypes.Structure):

@@ -1169,6 +1169,31 @@ class HipBackend:
         self.red_epoch += 1
         _lib.check(self.lib.x3d_diag_max_sum(self.h, f.ptr, self._dims(loc), VP(int(row_ptr))))
 
+    # ------------------------------------------------------------ explicit LES (csrc/les.hip)
+    LES_MODELS = {"smagorinsky": 0, "wale": 1}  # X3D_LES_* of include/x3d2_hip.h
+
+    def les_stress(self, grads, model, c2, widths, ih, row_ptr):
+        """the nine gradient fields (compute_vorticity's order) -> the subgrid stress and the eddy viscosity, in place
+        (tau_11, tau_12, tau_13, nu_t, tau_22, tau_23 in grads[0..5], tau_33 in grads[8]; grads[6], grads[7] untouched),
+        and the model's four scalars at the device address row_ptr; widths / ih = three device float64 tensors each
+        (h^(2/3) and 1 / h per local vertex of x, y, z).  No host synchronisation."""
+        if len(grads) != 9:
+            raise X3dError("les_stress: nine gradient fields expected")
+        if model not in self.LES_MODELS:
+            raise X3dError(f"les_stress: unknown model {model!r} (smagorinsky or wale)")
+        if not float(c2) >= 0.0:
+            raise X3dError("les_stress: the squared model constant must not be negative")
+        self._need_vert("les_stress", *grads)
+        dims = self.mesh.get_dims(VERT)
+        for tabs in (widths, ih):
+            for t, n in zip(tabs, dims):
+                if t.dtype != torch.float64 or not t.is_cuda or t.numel() < int(n):
+                    raise X3dError("les_stress: a width or spacing table is a device float64 tensor with one value per vertex")
+        prm = _lib.LesParams(self.LES_MODELS[model], float(c2), *[t.data_ptr() for t in list(widths) + list(ih)])
+        p = (VP * 9)(*[g.ptr for g in grads])
+        self.red_epoch += 1  # (the partials live in the reduction buffer)
+        _lib.check(self.lib.x3d_les_stress(self.h, p, _lib.ints(*dims), ctypes.byref(prm), VP(int(row_ptr))))
+
     # ------------------------------------------------------------ budget profiles (csrc/budget.hip)
     NBUDGET = 41  # X3D_NBUDGET of include/x3d2_hip.h
 

@@ -129,7 +129,8 @@ class BaseCase:
             # ibm%body masks the COMPLETED velocity with the BCs already stamped (base_case.f90:281-285): the new velocity
             # cannot be formed inside the pressure correction's first kernels then -- the explicit order
             walls, defer_upd = None, False
-        if s.fused and self.forcings_idle(it):
+        les = s.les
+        if s.fused and les is None and self.forcings_idle(it):
             # nothing touches the derivatives between transeq and the RK / AB stage: the last accumulation of
             # transeq may be folded into the stage's linear combination (Solver.transeq_fused)
             pending = s.transeq(deriv, curr, defer=True)
@@ -139,6 +140,10 @@ class BaseCase:
         else:
             s.transeq(deriv, curr)
             self.forcings(deriv[0], deriv[1], deriv[2], it)
+            if les is not None:
+                # the subgrid term reads the velocity transeq has completed (pending correction, bulk shift) and needs the
+                # derivatives stored: never the deferred branch above
+                les.add(deriv[0], deriv[1], deriv[2])
             if s.fused:
                 s.time_integrator.step(curr, deriv, s.dt, defer_update=defer_upd)
             else:
