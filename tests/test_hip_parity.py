@@ -1085,19 +1085,42 @@ def test_yz_operators_on_512_row_pencils(dims, bc, stretch):
             fo.data_loc = orc.VERT
 
 
-@pytest.mark.parametrize("switch", ["X3D_NO_DIRECT"])
+@pytest.mark.parametrize("switch", ["X3D_NO_DIRECT", "X3D_NO_Q5"])
 def test_wall_normal_pencils_in_their_other_forms(switch):
     """The 257-row Dirichlet pencils of the channel case (BASELINE configs[4]) through the form that is NOT the default:
     X3D_NO_DIRECT=1 -- the reference's distributed form on the lanes (scan_solve + the reduced 2 x 2 system), what every
     operator without DIRECT tables still runs.  The default, the DIRECT form (thomas_solve: the plain Thomas recurrences of
     the tridiagonal system tds.hip recovers from the preprocessed arrays), is what test_yz_operators_on_512_row_pencils
-    runs.  The switch is read once per process: child pytest runs of the 257- and 320-row cases (dims7, dims9, dims12)."""
+    runs.  The switch is read once per process: child pytest runs of the 257- and 320-row cases (dims7, dims9, dims12).
+    X3D_NO_Q5=1 -- the 320-row pencils (dims12) on the operators' own 6 rows per lane instead of 5 (csrc/ygen.hip)."""
+    import subprocess
+    import sys
+    cases = {"X3D_NO_DIRECT": "dims7 or dims9 or dims12", "X3D_NO_Q5": "dims12"}[switch]
+    r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-x", "-q", "-m", "gpu", "-k",
+                        "test_yz_operators_on_512_row_pencils and (%s)" % cases], env=dict(os.environ, **{switch: "1"}),
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:]
+    assert "%d passed" % len(cases.split(" or ")) in r.stdout, r.stdout[-3000:]
+
+
+@pytest.mark.parametrize("switch", ["X3D_NO_CIRC", "X3D_NO_UNIFORM"])
+def test_periodic_pencils_in_their_other_forms(switch):
+    """The periodic uniform pencils through the forms that are NOT the default, at TOL against the oracle:
+    X3D_NO_CIRC=1 -- the lane-table form (scan_solve on the preprocessed tables) in place of the circulant one (circ_solve),
+    the default of every periodic pencil the 64 lanes tile exactly since the circulant form came;
+    X3D_NO_UNIFORM=1 -- the general tables on a uniform grid (which also leaves the circulant form of the tile kernels and
+    of the 1024-row three-in-one kernel).
+    Child pytest runs of the seven periodic cases of test_yz_operators_on_512_row_pencils and of
+    test_x_direction_scan_kernels_full_size_pencils at 256, 512 and 1024 points.  Neither switch removes the three-in-one
+    launch of transeq_x (csrc/xscan.hip x3d_xscan_transeq3, csrc/xwide.hip x3d_xwide_transeq3: they pick the solve inside it),
+    so that test's counter assertion stays in force in these runs."""
     import subprocess
     import sys
     r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-x", "-q", "-m", "gpu", "-k",
-                        "test_yz_operators_on_512_row_pencils and (dims7 or dims9 or dims12)"], env=dict(os.environ, **{switch: "1"}),
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:]
+                        "(test_yz_operators_on_512_row_pencils and periodic) or "
+                        "(test_x_direction_scan_kernels_full_size_pencils and (256 or 512 or 1024))"],
+                       env=dict(os.environ, **{switch: "1"}), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "10 passed" in r.stdout, r.stdout[-3000:]
 
 
 def test_slab_poisson_solver_single_rank_emulation():

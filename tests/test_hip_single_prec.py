@@ -9,7 +9,12 @@ The Poisson solvers, path by path, on broadband right-hand sides (tests/poisson_
 FP64 reference is held to fp32_ref.BOUND = 8 x the FP32 yardstick of its case (tests/fp32_ref.py: the oracle's solve as a
 correctly rounded FP32 pipeline; tests/test_fp32_ref_host.py caps it and shows that the bound can fail), L2 against L2 and max
 norm against max norm.  The channel case and two-rank runs (tests/channel_sp_worker.py, test_hip_parity._run_ranks) at the
-step tolerances of this file: fields 2e-5 max(|ref|, 1), enstrophy 1e-5, max |div u| at FP32 round-off / the smallest spacing."""
+step tolerances of this file: fields 2e-5 max(|ref|, 1), enstrophy 1e-5, max |div u| at FP32 round-off / the smallest spacing.
+
+The compact operators, kernel family by kernel family and switch by switch (tests/ops_sp_worker.py), likewise: each result's
+error against the oracle in FP64 is held to fp32_ref.BOUND x the yardstick of its own check (tests/fp32_ops_ref.py: the dense
+operators as a correctly rounded FP32 pipeline; tests/test_fp32_ops_ref_host.py caps it and shows that the bound rejects a
+1e-5 defect which the 2e-5 / 5e-4 of the fixture tests above accept)."""
 import json
 import os
 import subprocess
@@ -368,3 +373,114 @@ def test_fp32_two_ranks_match_the_single_rank_fp64_run(nproc_dir, fused, dims, t
         assert np.max(np.abs(g[name] - w)) < 2e-5 * max(np.max(np.abs(w)), 1.0), name
     assert abs(rows[-1][1] - rrows[-1][1]) < 1e-5 * abs(rrows[-1][1])
     assert rows[-1][2] < _div_bound(2 * np.pi / max(dims)), rows[-1]
+
+
+# ---------------------------------------------------------------- the compact operators, kernel family by kernel family
+OPS_ENVS = {"default": {}, "no_npw2": {"X3D_NO_NPW2": "1"}, "no_circ": {"X3D_NO_CIRC": "1"}, "no_xcirc": {"X3D_NO_XCIRC": "1"},
+            "no_uniform": {"X3D_NO_UNIFORM": "1"}, "no_direct": {"X3D_NO_DIRECT": "1"}, "no_q5": {"X3D_NO_Q5": "1"}}
+_OPS_CLEAR = ("X3D_NO_CIRC", "X3D_NO_XCIRC", "X3D_NO_NPW2", "X3D_NO_UNIFORM", "X3D_NO_Q5", "X3D_NO_DIRECT", "X3D_NO_HALO_CIRC",
+              "X3D_NO_XSCAN", "X3D_XDIR_GENERIC", "X3D_XSCAN_P1", "X3D_NO_XWIDE", "X3D_NO_XWIDE_UPD", "X3D_NO_YTILE", "X3D_NO_ZTILE",
+              "X3D_NO_YGEN", "X3D_NO_TILE3", "X3D_NO_TDS_PAIR", "X3D_NO_TDS_LINCOMB", "X3D_NO_ONCHIP2", "X3D_NO_VIA_X", "X3D_PAD_X")
+
+
+def _ops_worker(name, tags, timeout=900):
+    """tests/ops_sp_worker.py over a group of cases with exactly the switches of OPS_ENVS[name] set"""
+    base = {k: v for k, v in os.environ.items() if k not in _OPS_CLEAR}
+    r = subprocess.run([sys.executable, os.path.join(HERE, "ops_sp_worker.py"), name, ",".join(tags)],
+                       capture_output=True, text=True, timeout=timeout, env=dict(base, X3D_SINGLE_PREC="1", **OPS_ENVS[name]))
+    print(r.stdout[-200000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("SPRESULT ")][-1][9:])
+
+
+@pytest.fixture(scope="module")
+def ops_runs():
+    """(environment, cases) -> results by case; a case runs once per environment, in one worker per call"""
+    done = {}
+
+    def get(name, tags):
+        todo = [t for t in tags if (name, t) not in done]
+        if todo:
+            for t, r in _ops_worker(name, todo).items():
+                done[name, t] = r
+        return {t: done[name, t] for t in tags}
+
+    return get
+
+
+def _accept_ops(res, what):
+    """every result of every case: finite, its yardstick under the cap, both errors within BOUND x the yardstick; -> the
+    number of results"""
+    import fp32_ops_ref as ops_ref
+    n, bad = 0, []
+    for tag, r in res.items():
+        assert len(r["ops"]) == 31, (what, tag, sorted(r["ops"]))
+        for name, e in r["ops"].items():
+            n += 1
+            assert e["finite"], (what, tag, name)
+            assert e["yard_max"] <= ops_ref.CAP, (what, tag, name, e["yard_max"])
+            if not (e["ratio_l2"] <= ops_ref.BOUND and e["ratio_max"] <= ops_ref.BOUND):
+                bad.append((tag, name, round(e["ratio_l2"], 2), round(e["ratio_max"], 2)))
+    assert not bad, (what, bad)
+    return n
+
+
+def _bits_differ(a, b):
+    """the names of the results whose bits differ between two runs of one case"""
+    return sorted(k for k in a["ops"] if a["ops"][k]["bits"] != b["ops"][k]["bits"])
+
+
+def _ops_groups():
+    import fp32_ops_ref as ops_ref
+    return {"x": ops_ref.X_PERIODIC + [ops_ref.X_NEUMANN], "yz_periodic": ops_ref.NPW2 + ops_ref.NPW1 + [ops_ref.NON_TILE],
+            "walls": ops_ref.WALLS}
+
+
+@pytest.mark.parametrize("group", ["x", "yz_periodic", "walls"])
+def test_fp32_operators_default_environment(ops_runs, group):
+    """every case of fp32_ops_ref.CASES, in three workers: x pencils of 128 .. 1024 points (LDS-tiled, generic and FAST scan
+    kernels, the 1024-row kernels, a Neumann pencil); periodic y / z pencils of 256 and 512 rows (tile kernels with two
+    pencils per wave and, at nx = 48, with one; the non-tile route at nx = 40); wall-normal pencils (K3g on 257, 320, 321,
+    384 and 500 rows, stretched and not, 130 Neumann rows).  Per case 31 results -- eight operators plain and accumulating,
+    both pairs in both modes, the direction's transeq plain and accumulating, Solver.transeq -- each within
+    fp32_ref.BOUND x the yardstick of its own check in both norms (tests/fp32_ops_ref.py)"""
+    import fp32_ops_ref as ops_ref
+    tags = _ops_groups()[group]
+    res = ops_runs("default", tags)
+    assert sorted(t for g in _ops_groups().values() for t in g) == sorted(ops_ref.CASES)
+    _accept_ops(res, "default")
+    if group == "x":
+        for tag, r in res.items():
+            assert r["extra"]["lincomb_bits_equal"], tag
+            if tag in ops_ref.X_PERIODIC and ops_ref.CASES[tag][0][0] in (256, 512, 1024):
+                assert r["extra"]["three_in_one"] == 1, (tag, r["extra"])  # the three-components-in-one kernels took transeq_x
+
+
+@pytest.mark.parametrize("name,group", [("no_npw2", "NPW2"), ("no_circ", "CIRC"), ("no_xcirc", "XCIRC"), ("no_uniform", "UNIFORM"),
+                                        ("no_direct", "DIRECT"), ("no_q5", "Q5")])
+def test_fp32_operators_in_their_other_forms(ops_runs, name, group):
+    """the forms a switch selects, on the cases it bears on, at the bound of the default run: one pencil per wave where two
+    are the default (X3D_NO_NPW2); the lane-table form of the periodic uniform pencils in place of the circulant one
+    (X3D_NO_CIRC; X3D_NO_XCIRC: of the three-in-one x kernel only); the general tables on a uniform grid (X3D_NO_UNIFORM); the
+    distributed form of the wall-normal pencils in place of the Thomas recurrences (X3D_NO_DIRECT); 6 rows per lane on 320-row
+    pencils in place of 5 (X3D_NO_Q5).
+    That a switch was honoured: X3D_NO_CIRC and X3D_NO_DIRECT select another algorithm, so in every case at least one result
+    differs in bits from the default run's.  The other switches re-tile or re-table the same arithmetic and may give the same
+    bits: which results differ is printed, nothing is asserted on it."""
+    import fp32_ops_ref as ops_ref
+    tags = getattr(ops_ref, group)
+    res = ops_runs(name, tags)
+    _accept_ops(res, name)
+    ref = ops_runs("default", tags)
+    for tag in tags:
+        differ = _bits_differ(res[tag], ref[tag])
+        kinds = sorted({k.split(".")[0] for k in differ})
+        line = json.dumps({"environment": name, "case": tag, "bits_differ": len(differ), "of": len(res[tag]["ops"]), "kinds": kinds})
+        print("FP32OPBITS " + line)
+        if os.environ.get("X3D_FP32_OPS_PROFILE"):  # (next to the workers' raw lines)
+            with open(os.environ["X3D_FP32_OPS_PROFILE"], "a") as fh:
+                fh.write(line + "\n")
+        if name in ("no_circ", "no_direct"):
+            assert differ, (name, tag)  # (identical bits throughout: the default form ran twice)
+        if tag.startswith("x.") and "three_in_one" in res[tag]["extra"] and ops_ref.CASES[tag][0][0] in (256, 512, 1024):
+            assert res[tag]["extra"]["three_in_one"] == 1, (name, tag)  # (none of these switches removes that launch)
