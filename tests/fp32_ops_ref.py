@@ -57,6 +57,15 @@ UNIFORM = ["y.32x512x8.periodic.uniform", "z.64x8x256.periodic.uniform"]
 DIRECT = ["y.32x257x8.dirichlet.top-bottom", "z.64x8x257.dirichlet.uniform", "y.32x320x8.dirichlet.top-bottom"]
 Q5 = ["y.32x320x8.dirichlet.top-bottom"]
 assert all(t in CASES for t in CIRC + XCIRC + UNIFORM + DIRECT + Q5)
+# pencil and tile counts that leave a tail: a persistent loop takes more than one trip and its last trip is short, or the
+# count is odd, or the last workgroup holds a lone pencil (tests/test_hip_work_counts.py has the arithmetic of each case).
+# After every other case: the seeds are 61 + the position
+COUNTS_X = [_case(dims, 1) for dims in ((256, 65, 64), (512, 9, 9), (1024, 9, 9), (1024, 46, 45))]
+COUNTS_TILE = [_case((128, 256, 66), 2), _case((64, 66, 512), 3), _case((48, 512, 87), 2)]
+COUNTS_WALLS = [_case(dims, 2, "dirichlet", "top-bottom", 0.259065151)
+                for dims in ((64, 257, 65), (32, 257, 9), (48, 257, 87), (32, 320, 9))]
+COUNTS = COUNTS_X + COUNTS_TILE + COUNTS_WALLS
+assert len(COUNTS) == 11 and [CASES[t][-1] for t in COUNTS] == list(range(83, 94))
 
 errors = fp32_ref.errors
 

@@ -30,8 +30,10 @@ def _pipeline(tag):
 
 
 def test_case_table():
-    """22 cases; the inputs are float32 and differ between the cases and between the three fields"""
-    assert len(ops_ref.CASES) == 22 and len({c[-1] for c in ops_ref.CASES.values()}) == 22
+    """33 cases, the last 11 the count-edge cases (COUNTS); the inputs are float32 and differ between the cases and between
+    the three fields"""
+    assert len(ops_ref.CASES) == 33 and len({c[-1] for c in ops_ref.CASES.values()}) == 33
+    assert list(ops_ref.CASES)[22:] == ops_ref.COUNTS
     for tag, (dims, d, bc, stretching, beta, L, seed) in ops_ref.CASES.items():
         u, v, w = ops_ref.inputs_of(tag)
         assert all(f.dtype == np.float32 and f.shape == dims[::-1] for f in (u, v, w)), tag

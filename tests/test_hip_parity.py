@@ -563,7 +563,10 @@ def test_two_rank_operators_vs_reference_two_rank_run(name, dn, fused, tmp_path)
 
 @pytest.mark.parametrize("dims,nproc,dn,fused", [((32, 16, 512), (1, 1, 2), "z", False), ((32, 16, 512), (1, 1, 2), "z", True),
                                                  ((32, 512, 16), (1, 2, 1), "y", True),
-                                                 ((32, 16, 1024), (1, 1, 2), "z", True)])
+                                                 ((32, 16, 1024), (1, 1, 2), "z", True),
+                                                 # 256 rows and 4 x 66 = 264 tiles per rank: the HALO forms' tile loop takes
+                                                 # a second, short trip (8 tiles on 256 workgroups)
+                                                 ((64, 66, 512), (1, 1, 2), "z", True), ((64, 512, 66), (1, 2, 1), "y", True)])
 def test_two_rank_single_pass_kernels_vs_oracle(dims, nproc, dn, fused, tmp_path):
     """256 / 512 points per rank along the split direction: the decomposed direction runs on the single-pass
     tile kernels (HALO forms: neighbour rows from the exchange, own boundary values out, boundary-strip
@@ -918,75 +921,11 @@ def test_x_direction_scan_kernels_full_size_pencils(nx):
     or, generic path, any n <= 512 that 64 lanes cover (192, 500); 128 uses the LDS-tiled kernels;
     1024 -> Q = 16 with compressed lane tables (csrc/xwide.hip, the channel case's x pencils).
     Every x operator, transeq_x, and the fused driver's accumulating forms against the oracle."""
-    from oracle import x3d_oracle as orc
-    from x3d2_amd import Mesh
-    from x3d2_amd.backend import HipBackend
-    from x3d2_amd.common import DIR_X, VERT, move_data_loc
-    from x3d2_amd.solver import Solver, SolverConfig
-    dims = (nx, 12, 10)
-    L = (6.283185307179586, 2.0, 3.0)
-    per = ("periodic",) * 2
-    mesh = Mesh(dims, (1, 1, 1), L, per, per, per)
-    s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True))
-    om = orc.Mesh(list(dims), [1, 1, 1], list(L), list(per), list(per), list(per))
-    o = orc.Solver(om, poisson="CG")
-    rng = np.random.default_rng(nx)
-    b, al = s.backend, s.backend.allocator
-    fields = []
-    for fo, fp in ((o.u, s.u), (o.v, s.v), (o.w, s.w)):
-        a = rng.standard_normal((10, 12, nx))
-        fo.data_loc = orc.VERT
-        o.backend.set_field_data(fo, a)
-        fp.set_data_loc(VERT)
-        b.set_field_data(fp, a)
-        fields.append(a)
-    # all 8 operators along x
-    for op in OPNAMES:
-        t_h, t_o = getattr(s.xdirps, op), getattr(o.xdirps, op)
-        src_h, src_o = al.get_block(DIR_X, VERT), o.backend.get_block(orc.DIR_X, orc.VERT)
-        b.veccopy(src_h, s.u)
-        src_o.data[...] = o.u.data
-        if op.endswith("p2v"):
-            src_h.set_data_loc(move_data_loc(VERT, 1, 1))
-            src_o.data_loc = orc.move_data_loc(orc.VERT, 1, 1)
-        out_h, out_o = al.get_block(DIR_X), o.backend.get_block(orc.DIR_X)
-        b.tds_solve(out_h, src_h, t_h)
-        o.backend.tds_solve(out_o, src_o, t_o)
-        ref = o.backend.get_field_data(out_o)
-        assert relerr(b.get_field_data(out_h), ref) < TOL, op
-        # accumulating form: out += -0.5 * T(u)
-        b.tds_apply(out_h, src_h, t_h, DIR_X, accumulate=True, scale=-0.5)
-        assert relerr(b.get_field_data(out_h), 0.5 * ref) < TOL, op + " (accumulate)"
-        for f in (src_h, out_h):
-            al.release_block(f)
-    # the RK stage's linear combination as the prologue of an x operator (x3d_tds_solve_lincomb): same bits as
-    # lincomb followed by tds_solve
-    y1, y2, d1, d2 = (al.get_block(DIR_X, VERT) for _ in range(4))
-    coefs = [0.3, -1.7, 0.01]
-    b.lincomb(y1, s.u, coefs, [s.v, s.w, s.u])
-    b.tds_apply(d1, y1, s.xdirps.stagder_v2p, DIR_X)
-    b.tds_lincomb(d2, s.xdirps.stagder_v2p, DIR_X, y2, s.u, coefs, [s.v, s.w, s.u])
-    for f in (d1, d2):
-        f.set_data_loc(move_data_loc(VERT, 1, 1))
-    assert np.array_equal(b.get_field_data(y1), b.get_field_data(y2))
-    assert np.array_equal(b.get_field_data(d1), b.get_field_data(d2))
-    for f in (y1, y2, d1, d2):
-        al.release_block(f)
-    # transeq along x only, then the whole fused right-hand side (x writes, y and z accumulate)
-    rhs_h = [al.get_block(DIR_X) for _ in range(3)]
-    rhs_o = [o.backend.get_block(orc.DIR_X) for _ in range(3)]
-    n3 = int(b.lib.x3d_backend_counter(b.h, 0))
-    b.transeq_x(*rhs_h, s.u, s.v, s.w, s.nu, s.xdirps)
+    from util import x_operator_battery
     fallback = any(os.environ.get(k) == "1" for k in ("X3D_XDIR_GENERIC", "X3D_NO_XSCAN", "X3D_XSCAN_P1", "X3D_NO_TILE3"))
-    if nx in (256, 512, 1024) and not fallback:  # the three-components-in-one kernels took it
-        assert int(b.lib.x3d_backend_counter(b.h, 0)) == n3 + 1
-    o.backend.transeq_x(*rhs_o, o.u, o.v, o.w, o.nu, o.xdirps)
-    for fh, fo, nm in zip(rhs_h, rhs_o, "uvw"):
-        assert relerr(b.get_field_data(fh, VERT), o.backend.get_field_data(fo, orc.VERT)) < TOL, nm
-    s.transeq(rhs_h, [s.u, s.v, s.w])
-    o.transeq(rhs_o, [o.u, o.v, o.w])
-    for fh, fo, nm in zip(rhs_h, rhs_o, "uvw"):
-        assert relerr(b.get_field_data(fh, VERT), o.backend.get_field_data(fo, orc.VERT)) < TOL, nm
+    # nx in (256, 512, 1024) and no such switch: the three-components-in-one kernels take transeq_x (120 pencils: even)
+    x_operator_battery((nx, 12, 10), (6.283185307179586, 2.0, 3.0), nx, TOL,
+                       three_in_one=True if nx in (256, 512, 1024) and not fallback else None)
 
 
 @pytest.mark.parametrize("dims,bc,stretch", [
@@ -1002,87 +941,8 @@ def test_x_direction_scan_kernels_full_size_pencils(nx):
 def test_yz_operators_on_512_row_pencils(dims, bc, stretch):
     """y / z pencils of 512 (the bench size) and 256 rows: every operator incl. accumulating forms against
     the oracle.  These are the sizes at which the single-pass on-chip kernels (K1e, csrc/onchip.hip) engage."""
-    from oracle import x3d_oracle as orc
-    from x3d2_amd import Mesh
-    from x3d2_amd.backend import HipBackend
-    from x3d2_amd.common import DIR_X, VERT, move_data_loc
-    from x3d2_amd.solver import Solver, SolverConfig
-    L = (2.0, 3.0, 2.5)
-    per = ("periodic",) * 2
-    d = 2 if dims[1] >= 128 else 3
-    bcs = [per, (bc,) * 2 if d == 2 else per, (bc,) * 2 if d == 3 else per]
-    strs = ("uniform", stretch, "uniform")
-    beta = (1.0, 0.259065151 if stretch == "top-bottom" else 1.3, 1.0)
-    mesh = Mesh(dims, (1, 1, 1), L, *bcs, strs, beta)
-    s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True))
-    om = orc.Mesh(list(dims), [1, 1, 1], list(L), *[list(x) for x in bcs], stretching=strs, beta=beta)
-    o = orc.Solver(om, poisson="CG")
-    rng = np.random.default_rng(7)
-    b, al = s.backend, s.backend.allocator
-    for fo, fp in ((o.u, s.u), (o.v, s.v), (o.w, s.w)):
-        a = rng.standard_normal((dims[2], dims[1], dims[0]))
-        fo.data_loc = orc.VERT
-        o.backend.set_field_data(fo, a)
-        fp.set_data_loc(VERT)
-        b.set_field_data(fp, a)
-    dp_h, dp_o = (s.ydirps, o.ydirps) if d == 2 else (s.zdirps, o.zdirps)
-    for op in OPNAMES:
-        t_h, t_o = getattr(dp_h, op), getattr(dp_o, op)
-        loc = move_data_loc(VERT, d, 1) if op.endswith("p2v") else VERT
-        src_h, src_o = al.get_block(DIR_X, VERT), o.backend.get_block(orc.DIR_X, orc.VERT)
-        b.veccopy(src_h, s.u)
-        src_o.data[...] = o.u.data
-        src_h.set_data_loc(loc)
-        src_o.data_loc = loc
-        a_o, out_o = o.backend.get_block(d), o.backend.get_block(d)
-        o.backend.reorder(a_o, src_o, 10 + d)
-        o.backend.tds_solve(out_o, a_o, t_o)
-        ref = o.backend.get_field_data(out_o)
-        out_h = al.get_block(DIR_X)
-        b.tds_apply(out_h, src_h, t_h, d)
-        out_h.set_data_loc(out_o.data_loc)
-        assert relerr(b.get_field_data(out_h), ref) < TOL, op
-        b.tds_apply(out_h, src_h, t_h, d, accumulate=True, scale=0.25)
-        assert relerr(b.get_field_data(out_h), 1.25 * ref) < TOL, op + " (accumulate)"
-        for f in (src_h, out_h):
-            al.release_block(f)
-    rhs_h = [al.get_block(DIR_X) for _ in range(3)]
-    rhs_o = [o.backend.get_block(orc.DIR_X) for _ in range(3)]
-    s.transeq(rhs_h, [s.u, s.v, s.w])
-    o.transeq(rhs_o, [o.u, o.v, o.w])
-    for fh, fo, nm in zip(rhs_h, rhs_o, "uvw"):
-        assert relerr(b.get_field_data(fh, VERT), o.backend.get_field_data(fo, orc.VERT)) < TOL, nm
-
-    # operator pairs of the pressure correction (x3d_tds_solve_pair; one tile kernel for y pencils)
-    def oracle_op(fo, t_o):
-        src_o = o.backend.get_block(orc.DIR_X, orc.VERT)
-        src_o.data[...] = fo.data
-        src_o.data_loc = fo.data_loc
-        a_o, out_o = o.backend.get_block(d), o.backend.get_block(d)
-        o.backend.reorder(a_o, src_o, 10 + d)
-        o.backend.tds_solve(out_o, a_o, t_o)
-        return o.backend.get_field_data(out_o)
-    for opa, opb in (("interpl_v2p", "stagder_v2p"), ("interpl_p2v", "stagder_p2v")):
-        loc = VERT if opa.endswith("v2p") else move_data_loc(VERT, d, 1)
-        ins = [al.get_block(DIR_X), al.get_block(DIR_X)]
-        for f_, src in zip(ins, (s.u, s.v)):
-            b.veccopy(f_, src)
-            f_.set_data_loc(loc)
-        for fo in (o.u, o.v):
-            fo.data_loc = loc
-        o1, o2 = al.get_block(DIR_X), al.get_block(DIR_X)
-        ta, tb = getattr(dp_h, opa), getattr(dp_h, opb)
-        ra, rb2 = oracle_op(o.u, getattr(dp_o, opa)), oracle_op(o.v, getattr(dp_o, opb))
-        rb1 = oracle_op(o.u, getattr(dp_o, opb))
-        b.tds_pair(0, o1, None, ins[0], ins[1], ta, tb, d)
-        o1.set_data_loc(move_data_loc(loc, d, ta.move))
-        assert relerr(b.get_field_data(o1), ra + rb2) < TOL, (opa, opb, "mode 0")
-        b.tds_pair(1, o1, o2, ins[0], None, ta, tb, d)
-        o2.set_data_loc(move_data_loc(loc, d, tb.move))
-        assert relerr(b.get_field_data(o1), ra) < TOL, (opa, opb, "mode 1 / A")
-        assert relerr(b.get_field_data(o2), rb1) < TOL, (opa, opb, "mode 1 / B")
-        for fo in (o.u, o.v):
-            fo.data_loc = orc.VERT
+    from util import yz_operator_battery
+    yz_operator_battery(dims, bc, stretch, TOL)
 
 
 @pytest.mark.parametrize("switch", ["X3D_NO_DIRECT", "X3D_NO_Q5"])

@@ -377,10 +377,12 @@ def test_fp32_two_ranks_match_the_single_rank_fp64_run(nproc_dir, fused, dims, t
 
 # ---------------------------------------------------------------- the compact operators, kernel family by kernel family
 OPS_ENVS = {"default": {}, "no_npw2": {"X3D_NO_NPW2": "1"}, "no_circ": {"X3D_NO_CIRC": "1"}, "no_xcirc": {"X3D_NO_XCIRC": "1"},
-            "no_uniform": {"X3D_NO_UNIFORM": "1"}, "no_direct": {"X3D_NO_DIRECT": "1"}, "no_q5": {"X3D_NO_Q5": "1"}}
+            "no_uniform": {"X3D_NO_UNIFORM": "1"}, "no_direct": {"X3D_NO_DIRECT": "1"}, "no_q5": {"X3D_NO_Q5": "1"},
+            "reserve127": {"X3D_COMM_RESERVE_CUS": "127"}}
 _OPS_CLEAR = ("X3D_NO_CIRC", "X3D_NO_XCIRC", "X3D_NO_NPW2", "X3D_NO_UNIFORM", "X3D_NO_Q5", "X3D_NO_DIRECT", "X3D_NO_HALO_CIRC",
               "X3D_NO_XSCAN", "X3D_XDIR_GENERIC", "X3D_XSCAN_P1", "X3D_NO_XWIDE", "X3D_NO_XWIDE_UPD", "X3D_NO_YTILE", "X3D_NO_ZTILE",
-              "X3D_NO_YGEN", "X3D_NO_TILE3", "X3D_NO_TDS_PAIR", "X3D_NO_TDS_LINCOMB", "X3D_NO_ONCHIP2", "X3D_NO_VIA_X", "X3D_PAD_X")
+              "X3D_NO_YGEN", "X3D_NO_TILE3", "X3D_NO_TDS_PAIR", "X3D_NO_TDS_LINCOMB", "X3D_NO_ONCHIP2", "X3D_NO_VIA_X", "X3D_PAD_X",
+              "X3D_COMM_RESERVE_CUS")
 
 
 def _ops_worker(name, tags, timeout=900):
@@ -433,7 +435,7 @@ def _bits_differ(a, b):
 def _ops_groups():
     import fp32_ops_ref as ops_ref
     return {"x": ops_ref.X_PERIODIC + [ops_ref.X_NEUMANN], "yz_periodic": ops_ref.NPW2 + ops_ref.NPW1 + [ops_ref.NON_TILE],
-            "walls": ops_ref.WALLS}
+            "walls": ops_ref.WALLS, "counts": ops_ref.COUNTS}
 
 
 @pytest.mark.parametrize("group", ["x", "yz_periodic", "walls"])
@@ -454,6 +456,43 @@ def test_fp32_operators_default_environment(ops_runs, group):
             assert r["extra"]["lincomb_bits_equal"], tag
             if tag in ops_ref.X_PERIODIC and ops_ref.CASES[tag][0][0] in (256, 512, 1024):
                 assert r["extra"]["three_in_one"] == 1, (tag, r["extra"])  # the three-components-in-one kernels took transeq_x
+
+
+def test_fp32_operators_at_counts_that_leave_a_tail(ops_runs):
+    """the eleven count-edge cases (fp32_ops_ref.COUNTS; tests/test_hip_work_counts.py has what each count does to the
+    launches, FP32 where it differs: two pencils per wave halve the tiles of y.128x256x66 to 264 and of z.64x66x512 to 132),
+    31 results each within BOUND x the yardstick in both norms.  transeq_x in one launch at 4160 pencils of 256 points and at
+    81 and 2070 pencils of 1024; not at 81 pencils of 512 (x3d_xscan_transeq3 declines an odd count)"""
+    import fp32_ops_ref as ops_ref
+    res = ops_runs("default", _ops_groups()["counts"])
+    assert len(res) == 11 and _accept_ops(res, "default") == 11 * 31
+    for tag in ops_ref.COUNTS_X:
+        assert res[tag]["extra"]["lincomb_bits_equal"], tag
+        assert res[tag]["extra"]["three_in_one"] == (0 if tag == "x.512x9x9.periodic.uniform" else 1), (tag, res[tag]["extra"])
+
+
+def test_fp32_operators_with_cus_reserved_keep_their_bits(ops_runs):
+    """X3D_COMM_RESERVE_CUS=127 on the tile and wall-normal cases of COUNTS: 129 workgroups at most (256 for the 8-pencil ygen
+    form), so every persistent launch takes other trips -- z.64x66x512's 132 tiles, one trip by default, now two.  Accepted
+    at the same bound, and no result changes bits against the default run: a pencil's arithmetic does not depend on the
+    workgroup that takes it"""
+    import fp32_ops_ref as ops_ref
+    tags = ops_ref.COUNTS_TILE + ops_ref.COUNTS_WALLS
+    res = ops_runs("reserve127", tags)
+    _accept_ops(res, "reserve127")
+    ref = ops_runs("default", tags)
+    moved = {}
+    for tag in tags:
+        differ = _bits_differ(res[tag], ref[tag])
+        line = json.dumps({"environment": "reserve127", "case": tag, "bits_differ": len(differ), "of": len(res[tag]["ops"]),
+                           "kinds": sorted({k.split(".")[0] for k in differ})})
+        print("FP32OPBITS " + line)
+        if os.environ.get("X3D_FP32_OPS_PROFILE"):
+            with open(os.environ["X3D_FP32_OPS_PROFILE"], "a") as fh:
+                fh.write(line + "\n")
+        if differ:
+            moved[tag] = differ
+    assert not moved, moved
 
 
 @pytest.mark.parametrize("name,group", [("no_npw2", "NPW2"), ("no_circ", "CIRC"), ("no_xcirc", "XCIRC"), ("no_uniform", "UNIFORM"),

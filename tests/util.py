@@ -407,3 +407,227 @@ def hyperviscous_der2nd(dirps, mesh, alloc):
     for k, sym in (("der2nd", False), ("der2nd_sym", True)):
         setattr(dirps, k, alloc(n, float(mesh.d[d0]), "second-deriv", "compact6-hyperviscous", bc_s, bc_e, stretch=vds2,
                                 stretch_correct=vd2s, sym=sym, **HYPERVISCOUS))
+
+
+# ---------------------------------------------------------------- operator batteries against the oracle (GPU tests)
+# The bodies of test_hip_parity.py's test_x_direction_scan_kernels_full_size_pencils and
+# test_yz_operators_on_512_row_pencils, shared with tests/test_hip_work_counts.py.  `got`, when given, collects every
+# compared array of the product under the names tests/ops_sp_worker.py uses ("tds.<op>", "acc.<op>", "pair0.<a>+<b>",
+# "pair1.<a>.A", "pair1.<b>.B", "transeq_dir.<c>", "transeq_dir_acc.<c>", "transeq.<c>"), and `worst` the largest relerr
+# of the battery under "relerr".  full=True adds what one of the two bodies has and the other lacks, so that both give the
+# same 31 results: the pairs on x; the direction's transeq on y / z; its accumulating form on all three.
+def _pair_battery(s, o, d, dp_h, dp_o, tol, note):
+    """operator pairs of the pressure correction (x3d_tds_solve_pair; one tile kernel for y pencils)"""
+    from oracle import x3d_oracle as orc
+    from x3d2_amd.common import DIR_X, VERT, move_data_loc
+    b, al = s.backend, s.backend.allocator
+
+    def oracle_op(fo, t_o):
+        src_o = o.backend.get_block(orc.DIR_X, orc.VERT)
+        src_o.data[...] = fo.data
+        src_o.data_loc = fo.data_loc
+        out_o = o.backend.get_block(d)
+        if d == 1:
+            o.backend.tds_solve(out_o, src_o, t_o)
+        else:
+            a_o = o.backend.get_block(d)
+            o.backend.reorder(a_o, src_o, 10 + d)
+            o.backend.tds_solve(out_o, a_o, t_o)
+        return o.backend.get_field_data(out_o)
+    for opa, opb in (("interpl_v2p", "stagder_v2p"), ("interpl_p2v", "stagder_p2v")):
+        loc = VERT if opa.endswith("v2p") else move_data_loc(VERT, d, 1)
+        ins = [al.get_block(DIR_X), al.get_block(DIR_X)]
+        for f_, src in zip(ins, (s.u, s.v)):
+            b.veccopy(f_, src)
+            f_.set_data_loc(loc)
+        for fo in (o.u, o.v):
+            fo.data_loc = loc
+        o1, o2 = al.get_block(DIR_X), al.get_block(DIR_X)
+        ta, tb = getattr(dp_h, opa), getattr(dp_h, opb)
+        ra, rb2 = oracle_op(o.u, getattr(dp_o, opa)), oracle_op(o.v, getattr(dp_o, opb))
+        rb1 = oracle_op(o.u, getattr(dp_o, opb))
+        b.tds_pair(0, o1, None, ins[0], ins[1], ta, tb, d)
+        o1.set_data_loc(move_data_loc(loc, d, ta.move))
+        assert note("pair0.%s+%s" % (opa, opb), b.get_field_data(o1), ra + rb2) < tol, (opa, opb, "mode 0")
+        b.tds_pair(1, o1, o2, ins[0], None, ta, tb, d)
+        o2.set_data_loc(move_data_loc(loc, d, tb.move))
+        assert note("pair1.%s.A" % opa, b.get_field_data(o1), ra) < tol, (opa, opb, "mode 1 / A")
+        assert note("pair1.%s.B" % opb, b.get_field_data(o2), rb1) < tol, (opa, opb, "mode 1 / B")
+        for fo in (o.u, o.v):
+            fo.data_loc = orc.VERT
+        for f_ in ins + [o1, o2]:
+            al.release_block(f_)
+
+
+def _noter(got, worst):
+    def note(name, a, ref):
+        e = relerr(a, ref)
+        if got is not None and name is not None:
+            got[name] = a
+        if worst is not None:
+            worst["relerr"] = max(worst.get("relerr", 0.0), e)
+        return e
+    return note
+
+
+def x_operator_battery(dims, L, seed, tol, three_in_one=None, full=False, got=None, worst=None):
+    """periodic x pencils: every x operator, the lincomb prologue (bits), transeq_x and the fused driver's accumulating
+    forms against the oracle.  three_in_one: True / False -- the three-components-in-one counter rises by one / stays
+    across transeq_x; None: not asserted.  -> the product's solver"""
+    from oracle import x3d_oracle as orc
+    from x3d2_amd import Mesh
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.common import DIR_X, VERT, move_data_loc
+    from x3d2_amd.solver import Solver, SolverConfig
+    nx = dims[0]
+    note = _noter(got, worst)
+    per = ("periodic",) * 2
+    mesh = Mesh(dims, (1, 1, 1), L, per, per, per)
+    s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True))
+    om = orc.Mesh(list(dims), [1, 1, 1], list(L), list(per), list(per), list(per))
+    o = orc.Solver(om, poisson="CG")
+    rng = np.random.default_rng(seed)
+    b, al = s.backend, s.backend.allocator
+    fields = []
+    for fo, fp in ((o.u, s.u), (o.v, s.v), (o.w, s.w)):
+        a = rng.standard_normal((dims[2], dims[1], nx))
+        fo.data_loc = orc.VERT
+        o.backend.set_field_data(fo, a)
+        fp.set_data_loc(VERT)
+        b.set_field_data(fp, a)
+        fields.append(a)
+    # all 8 operators along x
+    for op in OPNAMES:
+        t_h, t_o = getattr(s.xdirps, op), getattr(o.xdirps, op)
+        src_h, src_o = al.get_block(DIR_X, VERT), o.backend.get_block(orc.DIR_X, orc.VERT)
+        b.veccopy(src_h, s.u)
+        src_o.data[...] = o.u.data
+        if op.endswith("p2v"):
+            src_h.set_data_loc(move_data_loc(VERT, 1, 1))
+            src_o.data_loc = orc.move_data_loc(orc.VERT, 1, 1)
+        out_h, out_o = al.get_block(DIR_X), o.backend.get_block(orc.DIR_X)
+        b.tds_solve(out_h, src_h, t_h)
+        o.backend.tds_solve(out_o, src_o, t_o)
+        ref = o.backend.get_field_data(out_o)
+        assert note("tds." + op, b.get_field_data(out_h), ref) < tol, op
+        # accumulating form: out += -0.5 * T(u)
+        b.tds_apply(out_h, src_h, t_h, DIR_X, accumulate=True, scale=-0.5)
+        assert note("acc." + op, b.get_field_data(out_h), 0.5 * ref) < tol, op + " (accumulate)"
+        for f in (src_h, out_h):
+            al.release_block(f)
+    if full:
+        _pair_battery(s, o, 1, s.xdirps, o.xdirps, tol, note)
+    # the RK stage's linear combination as the prologue of an x operator (x3d_tds_solve_lincomb): same bits as
+    # lincomb followed by tds_solve
+    y1, y2, d1, d2 = (al.get_block(DIR_X, VERT) for _ in range(4))
+    coefs = [0.3, -1.7, 0.01]
+    b.lincomb(y1, s.u, coefs, [s.v, s.w, s.u])
+    b.tds_apply(d1, y1, s.xdirps.stagder_v2p, DIR_X)
+    b.tds_lincomb(d2, s.xdirps.stagder_v2p, DIR_X, y2, s.u, coefs, [s.v, s.w, s.u])
+    for f in (d1, d2):
+        f.set_data_loc(move_data_loc(VERT, 1, 1))
+    assert np.array_equal(b.get_field_data(y1), b.get_field_data(y2))
+    assert np.array_equal(b.get_field_data(d1), b.get_field_data(d2))
+    for f in (y1, y2, d1, d2):
+        al.release_block(f)
+    # transeq along x only, then the whole fused right-hand side (x writes, y and z accumulate)
+    rhs_h = [al.get_block(DIR_X) for _ in range(3)]
+    rhs_o = [o.backend.get_block(orc.DIR_X) for _ in range(3)]
+    n3 = int(b.lib.x3d_backend_counter(b.h, 0))
+    b.transeq_x(*rhs_h, s.u, s.v, s.w, s.nu, s.xdirps)
+    if three_in_one is not None:  # True: the three-components-in-one kernels took it
+        assert int(b.lib.x3d_backend_counter(b.h, 0)) == n3 + (1 if three_in_one else 0)
+    o.backend.transeq_x(*rhs_o, o.u, o.v, o.w, o.nu, o.xdirps)
+    refs = [o.backend.get_field_data(fo, orc.VERT) for fo in rhs_o]
+    for fh, ref, nm in zip(rhs_h, refs, "uvw"):
+        assert note("transeq_dir." + nm, b.get_field_data(fh, VERT), ref) < tol, nm
+    if full:
+        _transeq_dir_acc(s, 1, s.xdirps, rhs_h, refs, fields, tol, note)
+    s.transeq(rhs_h, [s.u, s.v, s.w])
+    o.transeq(rhs_o, [o.u, o.v, o.w])
+    for fh, fo, nm in zip(rhs_h, rhs_o, "uvw"):
+        assert note("transeq." + nm, b.get_field_data(fh, VERT), o.backend.get_field_data(fo, orc.VERT)) < tol, nm
+    return s
+
+
+def _transeq_dir_acc(s, d, dp_h, rhs_h, refs, fields, tol, note):
+    """the direction's transeq added to other fields (w, u, v), against those fields + the oracle's plain result"""
+    from x3d2_amd.common import VERT
+    b = s.backend
+    prevs = (fields[2], fields[0], fields[1])
+    for f, prev in zip(rhs_h, (s.w, s.u, s.v)):
+        b.veccopy(f, prev)
+    b.transeq_dir(d, *rhs_h, s.u, s.v, s.w, s.nu, dp_h, accumulate=True)
+    for fh, ref, prev, nm in zip(rhs_h, refs, prevs, "uvw"):
+        assert note("transeq_dir_acc." + nm, b.get_field_data(fh, VERT), prev + ref) < tol, nm + " (accumulate)"
+
+
+def yz_operator_battery(dims, bc, stretch, tol, d=None, seed=7, full=False, got=None, worst=None):
+    """y / z pencils (d: 2 / 3; None: y where dims[1] >= 128): every operator incl. accumulating forms, Solver.transeq and
+    the operator pairs against the oracle.  -> the product's solver"""
+    from oracle import x3d_oracle as orc
+    from x3d2_amd import Mesh
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.common import DIR_X, VERT, move_data_loc
+    from x3d2_amd.solver import Solver, SolverConfig
+    note = _noter(got, worst)
+    L = (2.0, 3.0, 2.5)
+    per = ("periodic",) * 2
+    if d is None:
+        d = 2 if dims[1] >= 128 else 3
+    bcs = [per, (bc,) * 2 if d == 2 else per, (bc,) * 2 if d == 3 else per]
+    strs = ("uniform", stretch, "uniform")
+    beta = (1.0, 0.259065151 if stretch == "top-bottom" else 1.3, 1.0)
+    mesh = Mesh(dims, (1, 1, 1), L, *bcs, strs, beta)
+    s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True))
+    om = orc.Mesh(list(dims), [1, 1, 1], list(L), *[list(x) for x in bcs], stretching=strs, beta=beta)
+    o = orc.Solver(om, poisson="CG")
+    rng = np.random.default_rng(seed)
+    b, al = s.backend, s.backend.allocator
+    fields = []
+    for fo, fp in ((o.u, s.u), (o.v, s.v), (o.w, s.w)):
+        a = rng.standard_normal((dims[2], dims[1], dims[0]))
+        fo.data_loc = orc.VERT
+        o.backend.set_field_data(fo, a)
+        fp.set_data_loc(VERT)
+        b.set_field_data(fp, a)
+        fields.append(a)
+    dp_h, dp_o = (s.ydirps, o.ydirps) if d == 2 else (s.zdirps, o.zdirps)
+    for op in OPNAMES:
+        t_h, t_o = getattr(dp_h, op), getattr(dp_o, op)
+        loc = move_data_loc(VERT, d, 1) if op.endswith("p2v") else VERT
+        src_h, src_o = al.get_block(DIR_X, VERT), o.backend.get_block(orc.DIR_X, orc.VERT)
+        b.veccopy(src_h, s.u)
+        src_o.data[...] = o.u.data
+        src_h.set_data_loc(loc)
+        src_o.data_loc = loc
+        a_o, out_o = o.backend.get_block(d), o.backend.get_block(d)
+        o.backend.reorder(a_o, src_o, 10 + d)
+        o.backend.tds_solve(out_o, a_o, t_o)
+        ref = o.backend.get_field_data(out_o)
+        out_h = al.get_block(DIR_X)
+        b.tds_apply(out_h, src_h, t_h, d)
+        out_h.set_data_loc(out_o.data_loc)
+        assert note("tds." + op, b.get_field_data(out_h), ref) < tol, op
+        b.tds_apply(out_h, src_h, t_h, d, accumulate=True, scale=0.25)
+        assert note("acc." + op, b.get_field_data(out_h), 1.25 * ref) < tol, op + " (accumulate)"
+        for f in (src_h, out_h):
+            al.release_block(f)
+    rhs_h = [al.get_block(DIR_X) for _ in range(3)]
+    rhs_o = [o.backend.get_block(orc.DIR_X) for _ in range(3)]
+    if full:  # the direction's transeq alone, plain and accumulating
+        ins, outs = [o.backend.get_block(d) for _ in range(3)], [o.backend.get_block(d) for _ in range(3)]
+        for a_o, fo in zip(ins, (o.u, o.v, o.w)):
+            o.backend.reorder(a_o, fo, 10 + d)
+        (o.backend.transeq_y if d == 2 else o.backend.transeq_z)(*outs, *ins, o.nu, dp_o)
+        refs = [o.backend.get_field_data(f, orc.VERT) for f in outs]
+        b.transeq_dir(d, *rhs_h, s.u, s.v, s.w, s.nu, dp_h, accumulate=False)
+        for fh, ref, nm in zip(rhs_h, refs, "uvw"):
+            assert note("transeq_dir." + nm, b.get_field_data(fh, VERT), ref) < tol, nm
+        _transeq_dir_acc(s, d, dp_h, rhs_h, refs, fields, tol, note)
+    s.transeq(rhs_h, [s.u, s.v, s.w])
+    o.transeq(rhs_o, [o.u, o.v, o.w])
+    for fh, fo, nm in zip(rhs_h, rhs_o, "uvw"):
+        assert note("transeq." + nm, b.get_field_data(fh, VERT), o.backend.get_field_data(fo, orc.VERT)) < tol, nm
+    _pair_battery(s, o, d, dp_h, dp_o, tol, note)
+    return s
