@@ -79,6 +79,10 @@ int x3d_backend_create_like(x3d_backend **out, const x3d_backend *like, const in
  * 3 -> times an entry point made the host wait for the stream to hand a reduction's result over (the reductions,
  *      x3d_slice_max_sum, x3d_outflow_params_get) */
 long x3d_backend_counter(const x3d_backend *b, int which);
+/* the resolved value of an environment switch of the library (README, "Switches"): a backend reads them ONCE, when
+ * x3d_backend_create makes it (x3d_backend_create_like: the values of `like`), and nothing later looks at the environment.
+ * b == NULL: what x3d_backend_create would store now (needs no GPU).  A name the library does not declare is an error. */
+int x3d_backend_switch(const x3d_backend *b, const char *name, long *value);
 int x3d_backend_set_stream(x3d_backend *b, void *stream);
 /* round 5: CUs the persistent kernels (one workgroup per CU for a whole launch: the tile and scan kernels) leave FREE, so that
  * kernels of other streams -- RCCL's send / recv kernels of an exchange meant to run beside them -- find a CU to start on

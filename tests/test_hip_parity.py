@@ -2037,3 +2037,150 @@ def test_channel_rk_stage_inside_the_z_launch_is_bit_identical(dims, monkeypatch
         del case, s
     for a, b in zip(out["0"], out["1"]):
         assert np.array_equal(a, b)
+
+
+# ---------------------------------------------------------------- switches belong to their owner, not to the process
+def _x_backend(monkeypatch, env):
+    """a solver on the x_operator_battery shape made under `env`, which is gone from the environment when this returns"""
+    from x3d2_amd import Mesh
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.solver import Solver, SolverConfig
+    dims, L, per = (256, 12, 10), (6.283185307179586, 2.0, 3.0), ("periodic",) * 2
+    for k in env:
+        monkeypatch.setenv(k, "1")
+    mesh = Mesh(dims, (1, 1, 1), L, per, per, per)
+    s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True))
+    for k in env:
+        monkeypatch.delenv(k)
+    return s
+
+
+def test_two_backends_in_one_process_keep_their_own_library_switches(monkeypatch):
+    """backend A made under a clean environment, backend B under X3D_NO_TILE3=1 X3D_NO_CIRC=1 (removed again before either
+    runs): transeq_x on A, B, A, B.  A takes the three-components-in-one kernel both times and B never -- a process-wide
+    cache would have fixed the first call's choice for both; each agrees with the oracle and repeats its own bits"""
+    from oracle import x3d_oracle as orc
+    from x3d2_amd.common import DIR_X, VERT
+    from util import library_switch_names
+    for k in library_switch_names():
+        monkeypatch.delenv(k, raising=False)
+    sa = _x_backend(monkeypatch, ())
+    sb = _x_backend(monkeypatch, ("X3D_NO_TILE3", "X3D_NO_CIRC"))
+    dims = tuple(int(v) for v in sa.mesh.get_dims(VERT))
+    per = ("periodic",) * 2
+    o = orc.Solver(orc.Mesh(list(dims), [1, 1, 1], [6.283185307179586, 2.0, 3.0], list(per), list(per), list(per)), poisson="CG")
+    rng = np.random.default_rng(256)
+    for k, fo in enumerate((o.u, o.v, o.w)):
+        a = rng.standard_normal((dims[2], dims[1], dims[0]))
+        fo.data_loc = orc.VERT
+        o.backend.set_field_data(fo, a)
+        for s in (sa, sb):
+            f = (s.u, s.v, s.w)[k]
+            f.set_data_loc(VERT)
+            s.backend.set_field_data(f, a)
+    rhs_o = [o.backend.get_block(orc.DIR_X) for _ in range(3)]
+    o.backend.transeq_x(*rhs_o, o.u, o.v, o.w, o.nu, o.xdirps)
+    refs = [o.backend.get_field_data(fo, orc.VERT) for fo in rhs_o]
+    out = {id(sa): [], id(sb): []}
+    for s in (sa, sb, sa, sb):
+        b = s.backend
+        rhs = [b.allocator.get_block(DIR_X) for _ in range(3)]
+        b.transeq_x(*rhs, s.u, s.v, s.w, s.nu, s.xdirps)
+        out[id(s)].append([b.get_field_data(f, VERT) for f in rhs])
+        for f in rhs:
+            b.allocator.release_block(f)
+    assert int(sa.backend.lib.x3d_backend_counter(sa.backend.h, 0)) == 2
+    assert int(sb.backend.lib.x3d_backend_counter(sb.backend.h, 0)) == 0
+    assert [sa.backend.lib_switch(k) for k in ("X3D_NO_TILE3", "X3D_NO_CIRC")] == [0, 0]
+    assert [sb.backend.lib_switch(k) for k in ("X3D_NO_TILE3", "X3D_NO_CIRC")] == [1, 1]
+    for s in (sa, sb):
+        first, second = out[id(s)]
+        for x, y, ref, nm in zip(first, second, refs, "uvw"):
+            assert relerr(x, ref) < TOL, nm
+            assert np.array_equal(x, y), nm
+
+
+def test_backend_created_like_another_inherits_its_switches(monkeypatch):
+    """x3d_backend_create_like copies the switches of the backend it is given and does not look at the environment"""
+    import ctypes
+    from x3d2_amd import _lib
+    from util import library_switch_names
+    names = library_switch_names()
+    for k in names:
+        monkeypatch.delenv(k, raising=False)
+    b = _x_backend(monkeypatch, ("X3D_NO_TILE3", "X3D_NO_CIRC")).backend
+    monkeypatch.setenv("X3D_NO_UNIFORM", "1")
+    child = ctypes.c_void_p()
+    _lib.check(b.lib.x3d_backend_create_like(ctypes.byref(child), b.h, _lib.ints(64, 12, 10)))
+    try:
+        def ask(h, name):
+            v = ctypes.c_long(-1)
+            _lib.check(b.lib.x3d_backend_switch(h, name.encode(), ctypes.byref(v)))
+            return int(v.value)
+        assert ask(None, "X3D_NO_UNIFORM") == 1 and ask(None, "X3D_NO_TILE3") == 0  # what the environment says now
+        for k in names:
+            assert ask(child, k) == ask(b.h, k) == b.lib_switch(k), k
+        assert ask(child, "X3D_NO_UNIFORM") == 0 and ask(child, "X3D_NO_TILE3") == 1 and ask(child, "X3D_NO_CIRC") == 1
+    finally:
+        b.lib.x3d_backend_destroy(child)
+
+
+@pytest.mark.parametrize("route", ["tile", "copies"])
+def test_driver_switch_is_fixed_when_the_solver_is_made(route, monkeypatch):
+    """the set-up of test_deferred_transeq_accumulation_is_bit_identical (RK3) with both solvers alive in one process: the
+    first made under X3D_NO_DEFER=1, which is gone from the environment before the second is made; stepped in turn, twice.
+    The first never defers, the second defers every stage of every variable, and their fields compare as that test's do
+    (route "copies", the z pencils through transposed copies: X3D_NO_ZTILE=1, a switch of the two backends)"""
+    from x3d2_amd import Mesh
+    from x3d2_amd.backend import HipBackend
+    from x3d2_amd.case import BaseCase
+    from x3d2_amd.common import VERT
+    from x3d2_amd.solver import Solver, SolverConfig
+    dims, L = (16, 256, 256), (2.0, 3.0, 2.5)
+    per = ("periodic",) * 2
+    rng = np.random.default_rng(11)
+    init = [0.3 * rng.standard_normal((dims[2], dims[1], dims[0])) for _ in range(3)]
+    name = "transeq_lincomb" if route == "tile" else "lincomb_pending"
+
+    class _Case(BaseCase):
+        def initial_conditions(self):
+            pass
+
+    def make():
+        mesh = Mesh(dims, (1, 1, 1), L, per, per, per)
+        s = Solver(HipBackend(mesh), mesh, SolverConfig(poisson_solver_type="CG", fused=True, time_intg="RK3", dt=1e-3, Re=100.0))
+        case = _Case(s)
+        for f, a in zip((s.u, s.v, s.w), init):
+            f.set_data_loc(VERT)
+            s.backend.set_field_data(f, a)
+        calls = {"n": 0}
+        real = getattr(s.backend, name)
+
+        def counted(*args, **kw):
+            calls["n"] += 1
+            return real(*args, **kw)
+        setattr(s.backend, name, counted)
+        return case, calls
+
+    for k in ("X3D_NO_DEFER", "X3D_STAGE_IN_TILE", "X3D_NO_EPI3", "X3D_NO_ZTILE"):
+        monkeypatch.delenv(k, raising=False)
+    # (the two older homes of the stage, as in that test: the default one has a test of its own)
+    monkeypatch.setenv("X3D_NO_EPI3", "1")
+    monkeypatch.setenv("X3D_STAGE_IN_TILE" if route == "tile" else "X3D_NO_ZTILE", "1")
+    monkeypatch.setenv("X3D_NO_DEFER", "1")
+    plain, n_plain = make()
+    monkeypatch.delenv("X3D_NO_DEFER")
+    fused, n_fused = make()
+    for k in ("X3D_STAGE_IN_TILE", "X3D_NO_EPI3", "X3D_NO_ZTILE"):
+        monkeypatch.delenv(k, raising=False)  # (nothing below looks at the environment)
+    for it in (1, 2):
+        plain.step(it)
+        fused.step(it)
+    assert n_plain["n"] == 0
+    assert n_fused["n"] == 3 * 2 * 3  # every stage of every variable, two steps
+    for fa, fb in zip((fused.solver.u, fused.solver.v, fused.solver.w), (plain.solver.u, plain.solver.v, plain.solver.w)):
+        a, b_ = fused.solver.backend.get_field_data(fa, VERT), plain.solver.backend.get_field_data(fb, VERT)
+        if route == "tile":
+            assert relerr(a, b_) < 1e-14  # (a few ulp: test_deferred_transeq_accumulation_is_bit_identical says why)
+        else:
+            assert np.array_equal(a, b_)

@@ -631,3 +631,14 @@ def yz_operator_battery(dims, bc, stretch, tol, d=None, seed=7, full=False, got=
         assert note("transeq." + nm, b.get_field_data(fh, VERT), o.backend.get_field_data(fo, orc.VERT)) < tol, nm
     _pair_battery(s, o, d, dp_h, dp_o, tol, note)
     return s
+
+
+def library_switch_names():
+    """the names of the library's switch table (x3d2_amd/csrc/switches.hip), in its order"""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "x3d2_amd", "csrc", "switches.hip")) as fh:
+        txt = fh.read()
+    body = txt[txt.index("g_table[] = {"):]
+    return re.findall(r'"(X3D_[A-Z0-9_]+)"', body[:body.index("\n};")])
+

@@ -115,6 +115,7 @@ PROTOTYPES = {
     "x3d_field_scale": (I, [VP, VP, D]),
     "x3d_field_shift": (I, [VP, VP, D]),
     "x3d_backend_counter": (ctypes.c_long, [VP, I]),
+    "x3d_backend_switch": (I, [VP, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]),
     "x3d_lincomb": (I, [VP, VP, VP, I, c_double_p, ctypes.POINTER(VP)]),
     "x3d_transeq_x_rot": (I, [VP, VP, VP, VP, VP, VP, VP, D, VP, VP, VP, VP, D, VP, c_int_p]),
     "x3d_transeq_x_update": (I, [VP, VP, VP, VP, VP, VP, VP, D, VP, VP, VP, VP, VP, VP, VP, VP, VP, D, c_int_p]),

@@ -9,7 +9,6 @@ happens in libx3d2_hip.so through the C ABI (include/x3d2_hip.h); this class
 only sequences calls and does the neighbour exchanges.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -19,6 +18,7 @@ from .common import (CELL, DIR_C, DIR_X, DIR_Y, DIR_Z, N_HALO, NULL_LOC, VERT, X
                      get_rdr_from_dirs, move_data_loc)
 from .field import Allocator
 from .parallel import Comm
+from .switches import Switches
 from .tdsops import Tdsops
 
 VP = ctypes.c_void_p
@@ -40,6 +40,7 @@ class HipBackend:
         are recorded, rewritten onto the fused kernels and run when a result has to be visible.  This is what the
         Fortran shim switches on for the unchanged solver.f90; one rank, op-granular driver (SolverConfig(fused=False))."""
         self.lib = _lib.load()
+        self.sw = Switches.from_env()  # (the one look at the environment: nothing below, and no later call, reads it again)
         if not torch.cuda.is_available():
             raise X3dError("x3d2_amd: no HIP device available -- the HIP backend has no CPU path")
         self.mesh = mesh
@@ -56,7 +57,7 @@ class HipBackend:
         pd = _lib.ints(0, 0, 0)
         _lib.check(self.lib.x3d_padded_dims(h, pd))
         self.padded_dims = tuple(pd)
-        self.allocator = Allocator(self.nblock, self.device)
+        self.allocator = Allocator(self.nblock, self.device, self.sw)
         # several ranks with exchanges that are meant to run BESIDE kernels (the overlapped path of parallel.Comm): the
         # persistent tile / scan kernels can leave X3D_COMM_RESERVE_CUS CUs free for the kernels of other streams
         # (csrc/common.h, comm_reserve)
@@ -66,21 +67,21 @@ class HipBackend:
         #  communication stream -- 8 or 16 reserved CUs changed nothing, profiles/r05_yslab_pipeline_timeline.txt; kept as
         #  a switch for the first run over real links, where RCCL's kernels want more room)
         del multi
-        self.comm_reserve = int(os.environ.get("X3D_COMM_RESERVE_CUS", "0"))
+        self.comm_reserve = self.sw.comm_reserve_cus
         _lib.check(self.lib.x3d_backend_set_comm_reserve(h, self.comm_reserve))
         # a decomposed direction that is periodic over all its ranks: its single-pass HALO kernels may take the open-ended
         # circulant solve (x3d_backend_set_ring; every rank holds the same mesh, so every rank says the same)
-        emul = os.environ.get("X3D_EMULATE_DECOMP", "").lower()
+        emul = self.sw.emulate_decomp.lower()
         for d in (2, 3):
             split = int(mesh.nproc_dir[d - 1]) > 1 or "xyz"[d - 1] in emul
             _lib.check(self.lib.x3d_backend_set_ring(h, d, int(split and bool(mesh.periodic_BC[d - 1]))))
-        self.lazy = (os.environ.get("X3D_LAZY") == "1") if lazy is None else bool(lazy)
+        self.lazy = self.sw.lazy if lazy is None else bool(lazy)
         self.red_epoch = 0  # bumped by every call that uses the library's reduction buffer (Solver.take_mean_shift)
         if self.lazy:
             # several ranks (round 4): the distributed entry points flush the queue and run at once on the buffers that
             # hold their handles' data; the local directions keep their rewrites.  (One process standing in for several
             # ranks, X3D_EMULATE_DECOMP, exchanges by slicing block memory directly: not with handles.)
-            if os.environ.get("X3D_EMULATE_DECOMP"):
+            if emul:
                 raise X3dError("deferred execution (lazy) does not serve X3D_EMULATE_DECOMP")
             _lib.check(self.lib.x3d_lazy_enable(h, 1))
             self.allocator.lazy = (self.lib, h)
@@ -88,7 +89,7 @@ class HipBackend:
         self._halo = {}
         self._tdsops = []
         self.before_read = []  # callables run before field data leaves the device (Solver.flush_grad)
-        self._emulate = os.environ.get("X3D_EMULATE_DECOMP", "").lower().replace("x", "")
+        self._emulate = emul.replace("x", "")
         self.halo_launches = 0  # single-pass launches on decomposed directions (tests assert the path engaged)
 
     def __del__(self):
@@ -128,6 +129,12 @@ class HipBackend:
 
     def sync(self):
         _lib.check(self.lib.x3d_device_sync(self.h))
+
+    def lib_switch(self, name):
+        """the value this backend's library side resolved for one of ITS switches (x3d_backend_switch)"""
+        v = ctypes.c_long()
+        _lib.check(self.lib.x3d_backend_switch(self.h, name.encode(), ctypes.byref(v)))
+        return int(v.value)
 
     LAZY_STATS = ("recorded", "launched", "aliases", "transeq_acc", "pairs", "tds_acc", "lincombs", "tds_lincomb",
                   "solve_000", "out_of_place", "materialised", "sync_copies", "flushes", "dropped", "transeq_upd",
@@ -310,7 +317,7 @@ class HipBackend:
         field are contiguous pieces of its block and are sent from there (X3D_PACK_Z_HALOS=1: through the pack
         kernel like y, for A/B runs)"""
         # (deferred execution: a block address is a handle, its rows may live in another buffer -- always pack)
-        return direction == DIR_Z and os.environ.get("X3D_PACK_Z_HALOS") != "1" and not self.lazy
+        return direction == DIR_Z and not self.sw.pack_z_halos and not self.lazy
 
     def _halo_exchange(self, direction, fields, n, hs, hr):
         """start the exchange of the boundary rows 1..4 / n-3..n of `fields` with the two neighbours of the
@@ -342,7 +349,7 @@ class HipBackend:
 
     def halo_tile_ok(self, direction, dirps):
         """the single-pass kernels take this decomposed direction's transeq (probe: a launch over zero planes)"""
-        if direction == DIR_X or not self._decomposed(direction) or os.environ.get("X3D_NO_HALO_TILE") == "1":
+        if direction == DIR_X or not self._decomposed(direction) or self.sw.no_halo_tile:
             return False
         key = ("tq_ok", direction, id(dirps))
         if key not in self._halo:
@@ -400,10 +407,10 @@ class HipBackend:
         mode, out1, out2, in1, in2, ta, tb = job
         key = ("tds_ok", direction, mode, id(ta), id(tb), bool(halo), int(yperm))
         if key not in self._halo:
-            if os.environ.get("X3D_NO_HALO_TILE") == "1" and halo:
+            if self.sw.no_halo_tile and halo:
                 self._halo[key] = False
             elif yperm:
-                ok = (halo and direction == DIR_Z and mode in (0, 1) and os.environ.get("X3D_NO_YPERM") != "1"
+                ok = (halo and direction == DIR_Z and mode in (0, 1) and not self.sw.no_yperm
                       and self.tds_tile_ok(direction, job, True))
                 if ok:  # (the probe of the interleaving form needs whole blocks: ask the launcher's own conditions)
                     ok = 0 < yperm <= int(self.mesh.vert_dims[1]) and yperm % 2 == 0
@@ -722,7 +729,7 @@ class HipBackend:
         """tds_pair along z next to the 010 Poisson solve, doing the solver's interleave of the first ny y rows on
         the way (mode 0: on out1, = enforce_periodicity_y of the result; mode 1: on in1, = undo_periodicity_y
         before the operators); False: not served for these pencils, nothing was done"""
-        if self._decomposed(DIR_Z) or os.environ.get("X3D_NO_YPERM") == "1":
+        if self._decomposed(DIR_Z) or self.sw.no_yperm:
             return False
         flag = ctypes.c_int(0)
         _lib.check(self.lib.x3d_tds_solve_pair_yperm(self.h, int(mode), out1.ptr,

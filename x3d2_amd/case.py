@@ -2,7 +2,6 @@
 the TGV case (src/case/tgv.f90), the channel (src/case/channel.f90), the cylinder (src/case/cylinder.f90) and the
 monitoring series
 (src/postprocess/monitoring.f90:46-90)."""
-import os
 import time
 
 import numpy as np
@@ -121,9 +120,9 @@ class BaseCase:
         # nothing reads the new velocity between the stage and the pressure correction when the case has no
         # BC hook: its update may then be formed inside the pressure correction's first kernels
         # (a case whose BC hook only stamps wall values hands them over instead: deferred_walls)
-        walls = self.deferred_walls() if s.fused and os.environ.get("X3D_NO_DEFER_WALLS") != "1" else None
+        walls = self.deferred_walls() if s.fused and not s.sw.no_defer_walls else None
         defer_upd = (s.fused and (type(self).apply_BC is BaseCase.apply_BC or walls is not None)
-                     and os.environ.get("X3D_NO_DEFER") != "1" and s.time_integrator.sname.upper().startswith("RK"))
+                     and not s.sw.no_defer and s.time_integrator.sname.upper().startswith("RK"))
         ibm = s.ibm
         if ibm is not None:
             # ibm%body masks the COMPLETED velocity with the BCs already stamped (base_case.f90:281-285): the new velocity
@@ -322,7 +321,7 @@ class ChannelCase(BaseCase):
         s, b = self.solver, self.solver.backend
         # ub -> 2/3, no host round trip on one rank; fused driver: the shift itself is left to transeq_x's kernel
         sh = None
-        if s.fused and os.environ.get("X3D_NO_ROT_FUSED") != "1":
+        if s.fused and not s.sw.no_rot_fused:
             # (round 6: the integral may have been taken by the kernel that formed this u, mean_target_of_next_BC)
             sh = s.take_mean_shift(s.u, 2.0 / 3.0) or b.field_mean_shift(s.u, 2.0 / 3.0)
         if sh is not None:
@@ -370,7 +369,7 @@ class ChannelCase(BaseCase):
         return self.bc_start_y
 
     def mean_target_of_next_BC(self):
-        return 2.0 / 3.0 if os.environ.get("X3D_NO_MEAN_IN_LINCOMB") != "1" else None
+        return 2.0 / 3.0 if not self.solver.sw.no_mean_in_lincomb else None
 
     def correction_deferrable(self):
         # define_BC reads the volume integral of u only, and the pending correction does not change it: dp/dx is a
@@ -381,7 +380,7 @@ class ChannelCase(BaseCase):
         # Offered where the x kernel takes the correction along: 1024-row x pencils (csrc/xwide.hip, k_xwide_transeq3_upd).
         s = self.solver
         return (s.fused and s.backend.comm.size == 1 and int(s.mesh.get_dims(VERT)[0]) == 1024
-                and os.environ.get("X3D_NO_ROT_FUSED") != "1" and os.environ.get("X3D_NO_CHANNEL_DEFER_GRAD") != "1"
+                and not s.sw.no_rot_fused and not s.sw.no_channel_defer_grad
                 and type(self).define_BC is ChannelCase.define_BC and type(self).apply_BC is ChannelCase.apply_BC)
 
     def forcings_idle(self, it):

@@ -48,9 +48,8 @@ PencilGeom x3d_geom(const x3d_backend *b, int dir)
     return g;
 }
 
-extern "C" int x3d_backend_create(x3d_backend **out, const int dims_vert[3], int device, void *stream)
+static int backend_create(x3d_backend **out, const int dims_vert[3], int device, void *stream, const x3d_switches &sw)
 {
-    X3D_RANGE(__func__);
     X3D_REQUIRE(out && dims_vert, "x3d_backend_create: null argument");
     X3D_REQUIRE(dims_vert[0] > 0 && dims_vert[1] > 0 && dims_vert[2] > 0,
                 "x3d_backend_create: dims must be positive");
@@ -61,6 +60,7 @@ extern "C" int x3d_backend_create(x3d_backend **out, const int dims_vert[3], int
     X3D_HIP(hipSetDevice(device));
     x3d_backend *b = new x3d_backend();
     memset(b, 0, sizeof *b);
+    b->sw = sw;
     b->device = device;
     b->prof_mask = ~0u;
     b->stream = (hipStream_t)stream;
@@ -74,8 +74,7 @@ extern "C" int x3d_backend_create(x3d_backend **out, const int dims_vert[3], int
         // contiguous-row x kernels lose a little in isolation (k_xscan_tds_lin 0.81 -> 0.89 ms; two segments:
         // 0.83), but the full step is the same for 16 / 32 / 48 / 80 doubles of padding: 49.0-49.6 ms against
         // 51.3 without (profiles/README.md).  3 % more memory.  X3D_PAD_X=<doubles> overrides (0: none).
-        const char *e = getenv("X3D_PAD_X");
-        if (e) b->nxp += (atoi(e) + 15) / 16 * 16;
+        if (b->sw.pad_x != X3D_SW_UNSET) b->nxp += ((int)b->sw.pad_x + 15) / 16 * 16;
         else if (b->nxp % 64 == 0 && b->nxp >= 256) b->nxp += 16;
     }
     b->nyp = b->ny;
@@ -99,11 +98,21 @@ extern "C" int x3d_backend_create(x3d_backend **out, const int dims_vert[3], int
     return 0;
 }
 
+// the switches are read from the environment here and nowhere later ...
+extern "C" int x3d_backend_create(x3d_backend **out, const int dims_vert[3], int device, void *stream)
+{
+    X3D_RANGE(__func__);
+    x3d_switches sw;
+    x3d_switches_from_env(&sw);
+    return backend_create(out, dims_vert, device, stream, sw);
+}
+
+// ... a backend made like another one makes that one's choices, whatever the environment says by then
 extern "C" int x3d_backend_create_like(x3d_backend **out, const x3d_backend *like, const int dims_vert[3])
 {
     X3D_RANGE(__func__);
     X3D_REQUIRE(like, "x3d_backend_create_like: null argument");
-    return x3d_backend_create(out, dims_vert, like->device, (void *)like->stream);
+    return backend_create(out, dims_vert, like->device, (void *)like->stream, like->sw);
 }
 
 extern "C" int x3d_backend_destroy(x3d_backend *b)

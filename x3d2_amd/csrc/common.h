@@ -132,7 +132,33 @@ struct PencilGeom {
     long s0, s1, rs;
 };
 
+// The library's environment switches, resolved ONCE per backend (switches.hip holds the table of names and the only getenv):
+// x3d_backend_create fills b->sw, x3d_backend_create_like copies it, and every launcher, *_ok query and constructor reads
+// it -- the query and the code that acts on its answer, and every rank of a ring, then make the same choice.  A flag is 1 when
+// its variable's first character is '1'.  All fields are long, so that x3d_backend_switch can report any of them.
+#define X3D_SW_UNSET (-0x7fffffffL - 1)
+struct x3d_switches {
+    long no_via_x, no_xscan, no_ygen, no_ytile, no_q5, no_direct, sfft010_split_xy;
+    long no_circ, no_halo_circ, no_uniform, xscan_p1, no_ztile, no_tds_pair, no_npw2, no_tile3, xdir_generic, no_xcirc;
+    long no_tds_lincomb, no_zfirst010, no_zfirst, no_xwide, no_xwide_upd;
+    long no_spectral_pad, no_fft512, no_rwt, no_r2c512, no_y010, y010_no_db, no_onchip2, no_slab_fused_z;
+    long lazy_dump, lazy_report, lazy_keep_zero_terms;
+    long pad_x;         // doubles of row padding; X3D_SW_UNSET: the backend's own rule (backend.hip)
+    long slab_z_split;  // -1 when unset
+    long lazy_rules;    // mask of the rewrite rules, all ones when unset
+    long y010_form;     // 0 split, 1 staged
+    // what several names decide together (none of these has a name of its own)
+    long via_x;         // the y / z operators through the x kernels' lane layout: !(NO_VIA_X | NO_XSCAN)
+    long ytile;         // the tile kernels: via_x && !NO_YTILE
+    long ygen;          // the general-length tile kernels: ytile && !NO_YGEN
+    long x_fast;        // the wave-per-pencil x kernels' derived forms: !(NO_XSCAN | XDIR_GENERIC)
+    long x_tq3;         // three components in one x launch: x_fast && !(NO_TILE3 | XSCAN_P1)
+    long x_circ;        // circulant solve in the x kernels: !(NO_CIRC | NO_XCIRC)
+};
+void x3d_switches_from_env(x3d_switches *sw);
+
 struct x3d_backend {
+    x3d_switches sw;
     int device;
     hipStream_t stream;
     int nx, ny, nz;     // local vertex dims

@@ -469,9 +469,7 @@ static int peers_run(x3d_backend *b, real2_t *R, long W, int npeers, const SpecS
     // -- 6 passes with 128-byte row segments instead of 2 with 64- / 32-byte ones.  Measured per solve at 512^3 per
     // rank (scratch/zstage_bench.py; transposes + rocFFT + division: 2.07 - 2.26 ms): 1 rank 0.76, 2 ranks 0.96,
     // 4 ranks 1.07 (split 1.62), 8 ranks 1.47 (split 1.86; 1.88 before the XCD-aware numbering of the mode groups)
-    static int split_env = -2;
-    if (split_env == -2) { const char *e = getenv("X3D_SLAB_Z_SPLIT"); split_env = e ? atoi(e) : -1; }
-    const bool split = npeers > 1 && split_env > 0 && PART == 0;
+    const bool split = npeers > 1 && b->sw.slab_z_split > 0 && PART == 0;
 #define LOCAL(NK_)                                                                                              \
     do {                                                                                                        \
         const int lds8 = sizeof(real2_t) * (8 * FP + 256);                                                      \

@@ -1075,8 +1075,7 @@ int x3d_lazy_flush_c(x3d_backend *b)
     x3d_lazy *L = b->lazy;
     if (!L || L->executing || L->q.empty()) return 0;
     L->stats[ST_FLUSHES]++;
-    static int dbg = -1;
-    if (dbg < 0) { const char *e = getenv("X3D_LAZY_DUMP"); dbg = e && e[0] == '1'; }
+    const bool dbg = b->sw.lazy_dump;
     if (dbg) dump(L, "recorded");
     optimise(b);
     if (dbg) dump(L, "rewritten");
@@ -1234,8 +1233,7 @@ extern "C" int x3d_lazy_enable(x3d_backend *b, int on)
     X3D_REQUIRE(b, "x3d_lazy_enable: null backend");
     x3d_lazy *L = lazy_of(b);
     if (on && std::find(g_reported.begin(), g_reported.end(), L) == g_reported.end()) {
-        const char *rep = getenv("X3D_LAZY_REPORT");
-        g_report_all = rep && rep[0] == '1';
+        g_report_all = b->sw.lazy_report;
         if (g_reported.empty()) atexit(report_at_exit);
         g_reported.push_back(L);
         g_reported_b.push_back(b);
@@ -1244,10 +1242,8 @@ extern "C" int x3d_lazy_enable(x3d_backend *b, int on)
         if (int rc = x3d_lazy_sync_c(b)) return rc;
     }
     L->on = on != 0;
-    const char *e = getenv("X3D_LAZY_KEEP_ZERO_TERMS");
-    L->keep_zero_terms = e && e[0] == '1';
-    const char *r = getenv("X3D_LAZY_RULES");
-    L->rules = r ? (unsigned)strtoul(r, nullptr, 0) : ~0u;
+    L->keep_zero_terms = b->sw.lazy_keep_zero_terms;
+    L->rules = (unsigned)b->sw.lazy_rules;
     return 0;
 }
 

@@ -65,10 +65,7 @@ extern "C" int x3d_poisson_create(x3d_backend *b, x3d_poisson **out, const int n
     memset(p, 0, sizeof *p);
     p->b = b;
     p->nx = n[0]; p->ny = n[1]; p->nz = n[2]; p->nxm = n[0] / 2 + 1;
-    {
-        const char *e = getenv("X3D_NO_SPECTRAL_PAD");  // (A/B: dense rows as in round 1)
-        p->nxs = (e && e[0] == '1') ? p->nxm : (p->nxm + 7) / 8 * 8;
-    }
+    p->nxs = b->sw.no_spectral_pad ? p->nxm : (p->nxm + 7) / 8 * 8;  // (X3D_NO_SPECTRAL_PAD=1, A/B: dense rows as in round 1)
     const size_t rows = (size_t)p->nz * p->ny, ns = rows * p->nxs;
     {   // (room for the z-first layout of the same spectrum too: [nz / 2 + 1][ny][nx + 16], csrc/zfirst.hip)
         const size_t nzf = (size_t)(p->nz / 2 + 1) * p->ny * (p->nx + 16);
@@ -97,8 +94,7 @@ extern "C" int x3d_poisson_create(x3d_backend *b, x3d_poisson **out, const int n
     X3D_FFT(hipfftMakePlanMany(p->plan_bw, 3, dims, cembed, 1, (int)ns, rembed, 1, (int)b->nblock, X3D_FFT_C2R, 1,
                                &ws[1]));
     if (int rc = fft_plans_share_work(pl, ws, nullptr, 2, &p->work, &p->work_size)) return rc;
-    const char *no512 = getenv("X3D_NO_FFT512");
-    if (p->ny == 512 && p->nz == 512 && !(no512 && no512[0] == '1')) {
+    if (p->ny == 512 && p->nz == 512 && !b->sw.no_fft512) {
         // batched 1-D r2c / c2r along x straight on the pitched block (rows nxp apart -> nxs complex)
         int nn[1] = {p->nx}, re[1] = {b->nxp}, ce[1] = {p->nxs};
         const int batch = p->ny * p->nz;
@@ -108,8 +104,7 @@ extern "C" int x3d_poisson_create(x3d_backend *b, x3d_poisson **out, const int n
         if (int rc = x3d_fft512_init()) return rc;
         p->fast512 = 1;
         {   // z-fastest reciprocal wave numbers for the fused z pass (spectral division in the transform's layout)
-            const char *no_rwt = getenv("X3D_NO_RWT");
-            if (!(no_rwt && no_rwt[0] == '1')) {
+            if (!b->sw.no_rwt) {
                 const size_t nsr = (size_t)p->nz * p->ny * p->nxs;
                 std::vector<real_t> h(nsr, 0.0);  // (pad columns: 0)
                 for (int k = 0; k < p->nz; k++)
@@ -122,8 +117,7 @@ extern "C" int x3d_poisson_create(x3d_backend *b, x3d_poisson **out, const int n
                 X3D_HIP(hipMemcpy(p->rwT, h.data(), sizeof(real_t) * nsr, hipMemcpyHostToDevice));
             }
         }
-        const char *no_r2c = getenv("X3D_NO_R2C512");
-        p->r2c512 = p->nx == 512 && (batch % 2) == 0 && !(no_r2c && no_r2c[0] == '1');
+        p->r2c512 = p->nx == 512 && (batch % 2) == 0 && !b->sw.no_r2c512;
     }
     *out = p;
     return 0;
@@ -481,7 +475,6 @@ extern "C" int x3d_poisson_solve_010(x3d_poisson *p, real_t *f, real_t *temp)
 
 int x3d_y010_run(x3d_backend *b, real2_t *c, int nxs, int nx, int ny, int nz, int mode, const real_t *tables, int sym,
                  real_t *const lu[2], bool *done, int nzl = 0);
-#define Y010_DEFAULT_FORM 1  // staged (y010.hip has the measurements)
 
 // plans of the y-last form: 2-D transforms over (z, x) -- r2c along x on the pitched block, c2c along z -- batched over
 // the y rows (the middle dimension of both layouts is the batch: plane pitch as the inner embedding)
@@ -489,11 +482,10 @@ static int y010_setup(x3d_poisson *p)
 {
     if (p->y010) return 0;
     p->y010 = -1;
-    const char *e = getenv("X3D_NO_Y010");
     x3d_backend *b = p->b;
     // (only the stretched solve takes the y-last path: no plans, no larger work area -- and no implicit device sync inside
     //  a step -- for anything else)
-    if ((e && e[0] == '1') || !p->stretched || p->ny != 256 || p->nxs % 8 != 0) return 0;
+    if (b->sw.no_y010 || !p->stretched || p->ny != 256 || p->nxs % 8 != 0) return 0;
     int nn[2] = {p->nz, p->nx};
     int re[2] = {b->nzp, b->nyp * b->nxp}, ce[2] = {p->nz, p->ny * p->nxs};
     // a plan that cannot be made is not an error of the solve: the partial plans go, y010 stays -1, the 3-D path runs
@@ -550,9 +542,7 @@ extern "C" int x3d_poisson_solve_010_rows(x3d_poisson *p, real_t *f)
         // X3D_Y010_FORM: "split" = k_y010<0> ; k_penta_solve x 2 ; k_y010<1>.  "staged" = the forward sweeps on the
         // tile of the first kernel, the backward sweeps on the tile of the second, the factored operator staged in LDS
         // (k_y010<3> ; k_y010<4>)
-        const char *ef = getenv("X3D_Y010_FORM");
-        const int form = !ef || !ef[0] ? Y010_DEFAULT_FORM : (ef[0] == 's' && ef[1] == 't' ? 1 : 0);
-        if (form == 1) {
+        if (b->sw.y010_form == 1) {
             {
                 ProfScope ps(b, X3D_K_SPECTRAL);
                 if (int rc = x3d_y010_run(b, p->c, p->nxs, p->nx, p->ny, p->nz, 3, p->ab, p->sym, p->lu, &done)) return rc;

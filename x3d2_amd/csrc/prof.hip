@@ -16,7 +16,7 @@ bool x3d_roctx_on()
 {
     if (g_roctx.state == 0) {
         g_roctx.state = -1;
-        const char *e = getenv("X3D_ROCTX");
+        const char *e = getenv("X3D_ROCTX");  // (not in the table of switches.hip: asked before any backend exists, once per process)
         if (e && e[0] == '1') {
             const char *libs[3] = {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so"};
             for (const char *l : libs) {

@@ -82,18 +82,14 @@ extern "C" int x3d_sfft_create_parts(x3d_backend *b, x3d_sfft **out, const int n
     {
         // spectral rows padded to 8 complex numbers (128 B) like the single-rank solver's: the 128 / 256-byte row
         // segments of the strided passes are line-aligned (pad columns hold zeros, their wave numbers ones)
-        const char *e = getenv("X3D_NO_SPECTRAL_PAD");
         const int nxm = nglob[0] / 2 + 1;
-        p->nxs = (e && e[0] == '1') ? nxm : (nxm + 7) / 8 * 8;
+        p->nxs = b->sw.no_spectral_pad ? nxm : (nxm + 7) / 8 * 8;
     }
     p->pz = pz; p->rz = rz; p->zl = p->nz / pz; p->ys = p->ny / pz;
     X3D_REQUIRE(parts >= 1 && p->ys % parts == 0, "x3d_sfft_create: %d y modes per rank do not split into %d parts",
                 p->ys, parts);
     p->parts = parts; p->ysc = p->ys / parts;
-    {
-        const char *e = getenv("X3D_NO_SLAB_FUSED_Z");
-        p->fused_z = p->zl == 512 && (pz == 1 || pz == 2 || pz == 4 || pz == 8) && !(e && e[0] == '1');
-    }
+    p->fused_z = p->zl == 512 && (pz == 1 || pz == 2 || pz == 4 || pz == 8) && !b->sw.no_slab_fused_z;
     X3D_REQUIRE(p->nx <= b->nxp && p->ny == b->nyp && p->zl <= b->nzp, "x3d_sfft_create: local block mismatch");
     const size_t n0 = (size_t)p->zl * p->ny * p->nxs;
     X3D_HIP(hipMalloc(&p->c0, sizeof(real2_t) * n0));
@@ -162,10 +158,9 @@ extern "C" int x3d_sfft_forward_local(x3d_sfft *p, const real_t *f_in, real_t *s
     X3D_LAZY_IN(p->b, f_in);  // (deferred execution: flush, then the buffer that holds the field)
     {
         ProfScope ps(p->b, X3D_K_FFT, 1);
-        static int own = -1;  // single-kernel real-to-complex x pass (fft512.hip), as in the single-rank solver
-        if (own < 0) { const char *e = getenv("X3D_NO_R2C512"); own = (e && e[0] == '1') ? 0 : 1; }
         const long rows = (long)p->zl * p->ny;
-        if (own && p->nx == 512 && rows % 2 == 0) {
+        // single-kernel real-to-complex x pass (fft512.hip), as in the single-rank solver
+        if (!p->b->sw.no_r2c512 && p->nx == 512 && rows % 2 == 0) {
             if (int rc = x3d_fft512_r2c(p->b, p->c0, f_in, rows, p->b->nxp, p->nxs)) return rc;
         } else {
             X3D_FFT(hipfftSetStream(p->plan_x_fw, p->b->stream));

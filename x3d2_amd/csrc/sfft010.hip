@@ -134,10 +134,7 @@ extern "C" int x3d_sfft010_create_parts(x3d_backend *b, x3d_sfft010 **out, const
                                                  X3D_FFT_R2C, p->zl, &ws[0]);
     const hipfftResult r_bw = hipfftMakePlanMany(p->plan_xy_bw, 2, nn, ce, 1, p->ny * p->nxs, re, 1, b->nxp * b->nyp,
                                                  X3D_FFT_C2R, p->zl, &ws[1]);
-    {
-        const char *e = getenv("X3D_SFFT010_SPLIT_XY");
-        p->split_xy = r_fw != HIPFFT_SUCCESS || r_bw != HIPFFT_SUCCESS || (e && e[0] == '1');
-    }
+    p->split_xy = r_fw != HIPFFT_SUCCESS || r_bw != HIPFFT_SUCCESS || b->sw.sfft010_split_xy;
     if (p->split_xy) {
         ws[0] = ws[1] = 0;
         int nx1[1] = {p->nx}, rx[1] = {b->nxp}, cx[1] = {p->nxs}, ny1[1] = {p->ny}, ey[1] = {p->ny};

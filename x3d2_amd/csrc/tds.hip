@@ -895,17 +895,6 @@ extern "C" long x3d_halo_row_size(const x3d_backend *b, int dir)
 // ------------------------------------------------------------------ launchers
 int x3d_onchip2_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t, int dir, int acc, real_t scale,
                     bool *done);  // onchip.hip (K1e)
-static bool use_onchip2()
-{
-    static int mode = -1;
-    if (mode < 0) {
-        // default on: single-pass solve for periodic 512-row y/z pencils, 0.50 ms vs 0.85 ms for the
-        // two-sweep pair (profiles/README.md); X3D_NO_ONCHIP2=1 falls back
-        const char *e = getenv("X3D_NO_ONCHIP2");
-        mode = (e && e[0] == '1') ? 0 : 1;
-    }
-    return mode == 1;
-}
 int x3d_transeq_via_x(x3d_backend *b, int dir, real_t *const r[3], const real_t *const f[3], real_t nu,
                       const x3d_tdsops *der1st, const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd,
                       const x3d_tdsops *der2nd_sym, int acc, bool *done);  // viax.hip
@@ -1025,7 +1014,9 @@ extern "C" int x3d_tds_solve_acc(x3d_backend *b, real_t *du, const real_t *u, co
     X3D_REQUIRE(du != u, "x3d_tds_solve: du and u must be distinct blocks");
     if (int rc = check_len(b, t, dir, "tds_solve")) return rc;
     if (dir == X3D_DIR_X) return x3d_xdir_tds(b, du, u, t, accumulate, scale);
-    if (use_onchip2()) {
+    // default on: single-pass solve for periodic 512-row y/z pencils, 0.50 ms vs 0.85 ms for the
+    // two-sweep pair (profiles/README.md); X3D_NO_ONCHIP2=1 falls back
+    if (!b->sw.no_onchip2) {
         bool done = false;
         if (int rc = x3d_onchip2_tds(b, du, u, t, dir, accumulate, scale, &done)) return rc;
         if (done) return 0;

@@ -76,16 +76,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static bool use_via_x()
-{
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = getenv("X3D_NO_VIA_X"), *f = getenv("X3D_NO_XSCAN");
-        mode = ((e && e[0] == '1') || (f && f[0] == '1')) ? 0 : 1;
-    }
-    return mode == 1;
-}
-
 struct ViaGeom {
     int nA, nB, nC;        // forward transpose: A = x (contiguous in the block), B = the pencil direction, C = the other
     long f_dA, f_dC, f_sB, f_sC;
@@ -141,7 +131,7 @@ int x3d_transeq_via_x(x3d_backend *b, int dir, real_t *const r[3], const real_t 
                       const x3d_tdsops *der2nd_sym, int acc, bool *done)
 {
     *done = false;
-    if (!use_via_x() || dir == X3D_DIR_X) return 0;
+    if (!b->sw.via_x || dir == X3D_DIR_X) return 0;
     if (!x3d_xscan_fast_ok(der1st, der1st_sym, der2nd) || !x3d_xscan_fast_ok(der1st_sym, der1st, der2nd_sym)) return 0;
     const int n = dir == X3D_DIR_Y ? b->ny : b->nz;
     if (der1st->n_tds != n) return 0;
@@ -285,7 +275,7 @@ extern "C" int x3d_transeq_defer(x3d_backend *b, int dir, real_t *pu, real_t *pv
     X3D_REQUIRE(b && pu && pv && pw && u && v && w && der1st && der1st_sym && der2nd && der2nd_sym && deferred,
                 "x3d_transeq_defer: null argument");
     *deferred = 0;
-    if (!use_via_x() || (dir != X3D_DIR_Y && dir != X3D_DIR_Z)) return 0;
+    if (!b->sw.via_x || (dir != X3D_DIR_Y && dir != X3D_DIR_Z)) return 0;
     if (x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd) &&
         x3d_ytile_applicable(b, dir, der1st_sym, der1st, der2nd_sym))
         return 0;  // the tile kernel + plain lincomb is faster than transposed copies + the fused RK stage
@@ -371,7 +361,7 @@ extern "C" int x3d_transeq_stage_ok(x3d_backend *b, int dir, const x3d_tdsops *d
 {
     X3D_RANGE(__func__);
     if (!b || !der1st || !der1st_sym || !der2nd || !der2nd_sym || (dir != X3D_DIR_Y && dir != X3D_DIR_Z)) return 0;
-    return use_via_x() && x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd) &&
+    return b->sw.via_x && x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd) &&
            x3d_ytile_applicable(b, dir, der1st_sym, der1st, der2nd_sym);
 }
 

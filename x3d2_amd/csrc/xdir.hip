@@ -373,41 +373,22 @@ __global__ void __launch_bounds__(64)
 }
 
 // ---------------------------------------------------------------- launchers
-static bool xdir_tiled()
-{
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = getenv("X3D_XDIR_GENERIC");
-        mode = (e && e[0] == '1') ? 0 : 1;
-    }
-    return mode == 1;
-}
-
 int x3d_xscan_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t, int acc, real_t scale, bool *done);
 int x3d_xwide_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t, int acc, real_t scale, bool *done,
                   real_t *psum = nullptr, int ny_sum = 0, int *nsum = nullptr);  // xwide.hip
 int x3d_xscan_transeq(x3d_backend *b, real_t *rhs, const real_t *u, const real_t *conv, real_t nu,
                       const x3d_tdsops *t1, const x3d_tdsops *t2, const x3d_tdsops *t3, int acc, bool *done);
-static bool use_xscan()
-{
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = getenv("X3D_NO_XSCAN");
-        mode = (e && e[0] == '1') ? 0 : 1;
-    }
-    return mode == 1;
-}
 
 int x3d_xdir_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t, int acc, real_t scale)
 {
-    if (use_xscan() && xdir_tiled()) {
+    if (b->sw.x_fast) {
         bool done = false;
         if (int rc = x3d_xscan_tds(b, du, u, t, acc, scale, &done)) return rc;
         if (done) return 0;
         if (int rc = x3d_xwide_tds(b, du, u, t, acc, scale, &done)) return rc;  // 1024-row pencils (xwide.hip)
         if (done) return 0;
     }
-    if (!xdir_tiled()) return x3d_generic_tds_local(b, du, u, t, X3D_DIR_X, acc, scale);
+    if (b->sw.xdir_generic) return x3d_generic_tds_local(b, du, u, t, X3D_DIR_X, acc, scale);
     const int np = b->ny * b->nz, nw = (np + 63) / 64;
     {
         ProfScope ps(b, X3D_K_TDS_FWD, X3D_DIR_X);
@@ -430,12 +411,12 @@ int x3d_xdir_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *
 int x3d_xdir_transeq(x3d_backend *b, real_t *rhs, const real_t *u, const real_t *conv, real_t nu,
                      const x3d_tdsops *t1, const x3d_tdsops *t2, const x3d_tdsops *t3, int acc)
 {
-    if (use_xscan() && xdir_tiled()) {
+    if (b->sw.x_fast) {
         bool done = false;
         if (int rc = x3d_xscan_transeq(b, rhs, u, conv, nu, t1, t2, t3, acc, &done)) return rc;
         if (done) return 0;
     }
-    if (!xdir_tiled()) return x3d_generic_transeq_local(b, X3D_DIR_X, rhs, u, conv, nu, t1, t2, t3, acc);
+    if (b->sw.xdir_generic) return x3d_generic_transeq_local(b, X3D_DIR_X, rhs, u, conv, nu, t1, t2, t3, acc);
     const int np = b->ny * b->nz, nw = (np + 63) / 64, npm = npmax_of(b);
     {
         ProfScope ps(b, X3D_K_TRANSEQ_FWD, X3D_DIR_X);

@@ -1502,33 +1502,19 @@ static bool stencil_narrow(const x3d_tdsops *t)
     return t->coeffs[0] == 0.0 && t->coeffs[1] == 0.0 && t->coeffs[7] == 0.0 && t->coeffs[8] == 0.0;
 }
 // the circulant form (circ_solve) where every operator of the launch offers it.  X3D_NO_CIRC=1: never (A/B)
-static bool circ_env_on()
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_CIRC"); on = (e && e[0] == '1') ? 0 : 1; }
-    return on == 1;
-}
 // the HALO (decomposed-direction) forms in the circulant form: the same predicate picks the main kernel's solve AND the strip
 // kernel's tables, on every rank (the operators are the same everywhere).  X3D_NO_HALO_CIRC=1: the table form (A/B)
-static bool halo_circ(const x3d_tdsops *t)
+static bool halo_circ(const x3d_backend *b, const x3d_tdsops *t)
 {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_HALO_CIRC"); on = (e && e[0] == '1') ? 0 : 1; }
-    return on && circ_env_on() && t->circ_open_ok && t->uniform && stencil_narrow(t);
-}
-static bool use_uniform_forms()
-{
-    static int uni_on = -1;
-    if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
-    return uni_on == 1;
+    return !b->sw.no_halo_circ && !b->sw.no_circ && t->circ_open_ok && t->uniform && stencil_narrow(t);
 }
 static bool pair_halo_circ(const x3d_backend *b, int dir, const x3d_tdsops *ta, const x3d_tdsops *tb)
 {
-    return b->ring[dir] && use_uniform_forms() && halo_circ(ta) && halo_circ(tb);
+    return b->ring[dir] && !b->sw.no_uniform && halo_circ(b, ta) && halo_circ(b, tb);
 }
 static bool transeq_halo_circ(const x3d_backend *b, int dir, const x3d_tdsops *der1st, const x3d_tdsops *der2nd)
 {
-    return b->ring[dir] && use_uniform_forms() && halo_circ(der1st) && halo_circ(der2nd);
+    return b->ring[dir] && !b->sw.no_uniform && halo_circ(b, der1st) && halo_circ(b, der2nd);
 }
 
 static bool xscan_ok(const x3d_tdsops *t) { return t->tab.TL != nullptr && (t->tab.Q == 4 || t->tab.Q == 8); }
@@ -1543,7 +1529,7 @@ int x3d_xscan_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops 
     // FAST: periodic-type stencils on a pencil the 64 lanes tile exactly, p2p or v2v (n_rhs == n_tds)
     const bool fast = t->tab.bulk_only && t->n_tds == 64 * Q && t->tab.n_rhs == t->n_tds && Q != 6;
     const bool narrow = stencil_narrow(t);
-    const bool circ = fast && narrow && t->uniform && t->circ_ok && circ_env_on();
+    const bool circ = fast && narrow && t->uniform && t->circ_ok && !b->sw.no_circ;
     const size_t lds = circ ? 0 : sizeof(real_t) * (LT_N(Q) * 64 + CS_N(Q));
     int blocks = (np + 7) / 8;
     const int cap = circ ? 1024 : 768;  // 43 KB of lane tables per 8-wave workgroup: 3 per CU; circulant form: no LDS, 4
@@ -1605,9 +1591,7 @@ int x3d_xscan_transeq_np(x3d_backend *b, real_t *rhs, const real_t *u, const rea
           : (acc ? launch_transeq<Q_, false, true, F_>(b, rhs, u, conv, nu, t1, t2, t3, np, blocks, lds, pitch)      \
                  : launch_transeq<Q_, false, false, F_>(b, rhs, u, conv, nu, t1, t2, t3, np, blocks, lds, pitch)))
 #define GO(Q_) (fast ? (narrow ? GO2(Q_, 2) : GO2(Q_, 1)) : GO2(Q_, 0))
-    static int p2 = -1;
-    if (p2 < 0) { const char *e = getenv("X3D_XSCAN_P1"); p2 = (e && e[0] == '1') ? 0 : 1; }  // same-box A/B: 0.61 -> 0.59 ms
-    if (p2 && fast && np % 2 == 0) {
+    if (!b->sw.xscan_p1 && fast && np % 2 == 0) {  // two pencils per wave, same-box A/B: 0.61 -> 0.59 ms
         const int blocks2 = x3d_persistent_blocks(b, (np / 2 + 7) / 8);
 #define LP2(Q_, S_, A_, N_)                                                                                    \
         do {                                                                                                   \
@@ -1650,16 +1634,6 @@ bool x3d_xscan_fast_ok(const x3d_tdsops *t1, const x3d_tdsops *t2, const x3d_tds
 }
 
 // K3y launcher: one transeq component along y, straight from / to the Cartesian block
-static bool use_ytile()
-{
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = getenv("X3D_NO_YTILE"), *f = getenv("X3D_NO_VIA_X"), *g = getenv("X3D_NO_XSCAN");
-        mode = ((e && e[0] == '1') || (f && f[0] == '1') || (g && g[0] == '1')) ? 0 : 1;  // (those two: two-sweep K1)
-    }
-    return mode == 1;
-}
-
 template <int Q, bool SAME, bool ACC, int FAST>
 static int launch_ytile(x3d_backend *b, real_t *rhs, const real_t *u, const real_t *conv, real_t nu,
                         const x3d_tdsops *t1, const x3d_tdsops *t2, const x3d_tdsops *t3, int share12, size_t lds,
@@ -1693,10 +1667,10 @@ static int launch_ytile(x3d_backend *b, real_t *rhs, const real_t *u, const real
 // transposed-copy route)
 bool x3d_ytile_applicable(x3d_backend *b, int dir, const x3d_tdsops *t1, const x3d_tdsops *t2, const x3d_tdsops *t3)
 {
-    if (!use_ytile() || !x3d_xscan_fast_ok(t1, t2, t3)) return false;
+    if (!b->sw.ytile || !x3d_xscan_fast_ok(t1, t2, t3)) return false;
     const int Q = t1->tab.Q;
     if ((dir == X3D_DIR_Y ? b->ny : b->nz) != 64 * Q || b->nx % 16 != 0) return false;
-    if (dir == X3D_DIR_Z) { const char *e = getenv("X3D_NO_ZTILE"); if (e && e[0] == '1') return false; }
+    if (dir == X3D_DIR_Z && b->sw.no_ztile) return false;
     const int share12 = t1->tl_hash == t2->tl_hash;
     return sizeof(real_t) * ((size_t)(share12 ? 2 : 3) * LT_N(Q) * 64 + 16 * (64 * Q + 4)) <= 160 * 1024;
 }
@@ -1728,14 +1702,10 @@ static int ytile_transeq_impl(x3d_backend *b, int dir, real_t *rhs, const real_t
                               const TileEpi *epi, bool *done)
 {
     *done = false;
-    if (!use_ytile() || !x3d_xscan_fast_ok(t1, t2, t3)) return 0;
+    if (!b->sw.ytile || !x3d_xscan_fast_ok(t1, t2, t3)) return 0;
     const int Q = t1->tab.Q;
     if ((dir == X3D_DIR_Y ? b->ny : b->nz) != 64 * Q || b->nx % 16 != 0) return 0;
-    if (dir == X3D_DIR_Z) {
-        static int zt = -1;  // z tiles: rows 2 MB apart; 1.03 ms per component against 1.6 through transposed copies
-        if (zt < 0) { const char *e = getenv("X3D_NO_ZTILE"); zt = (e && e[0] == '1') ? 0 : 1; }
-        if (!zt) return 0;
-    }
+    if (dir == X3D_DIR_Z && b->sw.no_ztile) return 0;  // z tiles: rows 2 MB apart; 1.03 ms per component against 1.6 through transposed copies
     const int share12 = t1->tl_hash == t2->tl_hash;
     const size_t lds = sizeof(real_t) * ((size_t)(share12 ? 2 : 3) * LT_N(Q) * 64 + 16 * (64 * Q + 4));
     if (lds > 160 * 1024) return 0;
@@ -1775,20 +1745,16 @@ int x3d_ytile_tds_pair(x3d_backend *b, int dir, int mode, real_t *out1, real_t *
                        bool *done)
 {
     *done = false;
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_TDS_PAIR"); on = (e && e[0] == '1') ? 0 : 1; }
-    if (!on || !use_ytile() || !xscan_ok(ta) || !xscan_ok(tb) || ta->tab.Q != tb->tab.Q) return 0;
+    if (b->sw.no_tds_pair || !b->sw.ytile || !xscan_ok(ta) || !xscan_ok(tb) || ta->tab.Q != tb->tab.Q) return 0;
     const int Q = ta->tab.Q;
     auto fast = [&](const x3d_tdsops *t) {
         return t->tab.bulk_only && t->n_tds == 64 * Q && t->tab.n_rhs == t->n_tds;
     };
     if (!fast(ta) || !fast(tb) || (dir == X3D_DIR_Y ? b->ny : b->nz) != 64 * Q || b->nx % 16 != 0) return 0;
-    if (dir == X3D_DIR_Z) { const char *e = getenv("X3D_NO_ZTILE"); if (e && e[0] == '1') return 0; }
+    if (dir == X3D_DIR_Z && b->sw.no_ztile) return 0;
     const bool narrow = stencil_narrow(ta) && stencil_narrow(tb);
-    static int uni_on = -1;
-    if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
-    const bool uni = uni_on && ta->uniform && tb->uniform;
-    const bool circ = narrow && uni && circ_env_on() && (halo ? pair_halo_circ(b, dir, ta, tb) : (ta->circ_ok && tb->circ_ok));
+    const bool uni = !b->sw.no_uniform && ta->uniform && tb->uniform;
+    const bool circ = narrow && uni && !b->sw.no_circ && (halo ? pair_halo_circ(b, dir, ta, tb) : (ta->circ_ok && tb->circ_ok));
     const size_t lds = sizeof(real_t) * ((size_t)(circ ? 0 : (mode == 2 ? 1 : 2) * LT_N(Q) * 64) + 16 * (64 * Q + 4) + (halo ? 128 + 64 : 0));
     if (lds > 160 * 1024) return 0;
     const long pxy = (long)b->nxp * b->nyp;
@@ -1827,7 +1793,7 @@ int x3d_ytile_tds_pair(x3d_backend *b, int dir, int mode, real_t *out1, real_t *
 // these two operators' z pair is served by the z-transforming form of the tile kernel on this backend's blocks
 bool x3d_zfirst_pairs_ok(const x3d_backend *b, const x3d_tdsops *ta, const x3d_tdsops *tb)
 {
-    if (!use_ytile() || !xscan_ok(ta) || !xscan_ok(tb) || ta->tab.Q != 8 || tb->tab.Q != 8) return false;
+    if (!b->sw.ytile || !xscan_ok(ta) || !xscan_ok(tb) || ta->tab.Q != 8 || tb->tab.Q != 8) return false;
     auto fast = [&](const x3d_tdsops *t) { return t->tab.bulk_only && t->n_tds == 512 && t->tab.n_rhs == t->n_tds; };
     if (!fast(ta) || !fast(tb) || b->nz != 512 || b->nx % 16 != 0) return false;
     if (sizeof(real_t) * ((size_t)2 * LT_NC(8) * 64 + ZF_AREA_DOUBLES + 512) > 160 * 1024) return false;
@@ -1850,10 +1816,8 @@ int x3d_ytile_tds_pair_zf(x3d_backend *b, int mode, real_t *out1, real_t *out2, 
     X3D_REQUIRE(zf.permn == 0 || (zf.permn == zf.ny && y0 == 0 && nyr == zf.ny), "tds_pair (z-first): interleaved rows, whole blocks only");
     if (nyr == 0) { *done = true; return 0; }
     const bool narrow = stencil_narrow(ta) && stencil_narrow(tb);
-    static int uni_on = -1;
-    if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
-    const bool uni = uni_on && ta->uniform && tb->uniform;
-    const bool circ = narrow && uni && circ_env_on() && ta->circ_ok && tb->circ_ok;
+    const bool uni = !b->sw.no_uniform && ta->uniform && tb->uniform;
+    const bool circ = narrow && uni && !b->sw.no_circ && ta->circ_ok && tb->circ_ok;
     const size_t lds = sizeof(real_t) * ((size_t)(circ ? 0 : 2 * LT_NC(8) * 64) + ZF_AREA_DOUBLES + 512);
     const long pxy = (long)b->nxp * b->nyp;
     const int ntx = b->nx / 16, ntiles = ntx * nyr, tile0 = ntx * y0;
@@ -1926,15 +1890,13 @@ int x3d_transeq_halo_fix_launch(x3d_backend *b, int dir, real_t *const r[3], con
 // at 256^3) -- two 256-row solves per wave double the solve phase for the bytes of one 512-row tile
 static int ytile_npw(const x3d_backend *b, bool halo)
 {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_NPW2"); on = (e && e[0] == '1') ? 0 : 1; }
-    return (on && !halo && b->nx % 32 == 0 && X3D_RB == 4) ? 2 : 1;
+    return (!b->sw.no_npw2 && !halo && b->nx % 32 == 0 && X3D_RB == 4) ? 2 : 1;
 }
 constexpr int NPW2 = X3D_RB == 4 ? 2 : 1;  // the NPW of the launches where npw == 2 (no two-pencil forms are built for FP64)
 
-static bool ytile_circ(const x3d_tdsops *a, const x3d_tdsops *a2, const x3d_tdsops *c, const x3d_tdsops *c2)
+static bool ytile_circ(const x3d_backend *b, const x3d_tdsops *a, const x3d_tdsops *a2, const x3d_tdsops *c, const x3d_tdsops *c2)
 {
-    return circ_env_on() && a->circ_ok && a2->circ_ok && c->circ_ok && c2->circ_ok;
+    return !b->sw.no_circ && a->circ_ok && a2->circ_ok && c->circ_ok && c2->circ_ok;
 }
 
 // K3y, three components in one launch (k_ytile_transeq3); f[0] is the advecting component.
@@ -1944,17 +1906,13 @@ int x3d_ytile_transeq3(x3d_backend *b, int dir, real_t *const r[3], const real_t
                        const x3d_tdsops *der2nd_sym, int acc, const TileHalo *halo, int other0, int nother, bool *done)
 {
     *done = false;
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_TILE3"); on = (e && e[0] == '1') ? 0 : 1; }
-    if (!on || !x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd)) return 0;
+    if (b->sw.no_tile3 || !x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd)) return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
     const int Q = der1st->tab.Q;
     const bool narrow = stencil_narrow(der1st) && stencil_narrow(der2nd);
-    static int uni_on = -1;
-    if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
-    const bool uni = uni_on && der1st->uniform && der1st_sym->uniform && der2nd->uniform && der2nd_sym->uniform;
+    const bool uni = !b->sw.no_uniform && der1st->uniform && der1st_sym->uniform && der2nd->uniform && der2nd_sym->uniform;
     const int npw = (narrow && uni) ? ytile_npw(b, halo != nullptr) : 1;  // (two pencils per wave: the uniform-grid forms)
-    const bool circ = narrow && uni && (halo ? transeq_halo_circ(b, dir, der1st, der2nd) : ytile_circ(der1st, der1st_sym, der2nd, der2nd_sym));
+    const bool circ = narrow && uni && (halo ? transeq_halo_circ(b, dir, der1st, der2nd) : ytile_circ(b, der1st, der1st_sym, der2nd, der2nd_sym));
     const size_t lds = sizeof(real_t) * ((size_t)(circ ? 0 : 2 * LT_N(Q) * 64) + 16 * npw * (64 * Q + 4) + (halo ? 256 + 288 : 0));
     if (lds > 160 * 1024) return 0;
     const long pxy = (long)b->nxp * b->nyp;
@@ -2008,15 +1966,13 @@ int x3d_ytile_transeq3_epi(x3d_backend *b, int dir, real_t *const r[3], const re
                            const x3d_tdsops *der2nd_sym, const TileEpi epi[3], bool *done)
 {
     *done = false;
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_TILE3"); on = (e && e[0] == '1') ? 0 : 1; }
-    if (!on || !x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd)) return 0;
+    if (b->sw.no_tile3 || !x3d_ytile_applicable(b, dir, der1st, der1st_sym, der2nd)) return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
     const int Q = der1st->tab.Q;
     const int npw = ytile_npw(b, false);
     // (FP64, 512 rows: the circulant form of THIS instantiation spills 14 VGPRs and runs at the table form's 3.1 ms; it is
     //  taken all the same -- the launch must give the bits of the plain z launch followed by the stage)
-    const bool circ = ytile_circ(der1st, der1st_sym, der2nd, der2nd_sym);
+    const bool circ = ytile_circ(b, der1st, der1st_sym, der2nd, der2nd_sym);
     const size_t lds = sizeof(real_t) * ((size_t)(circ ? 0 : 2 * LT_N(Q) * 64) + 16 * npw * (64 * Q + 4));
     const bool narrow = stencil_narrow(der1st) && stencil_narrow(der2nd);
     const bool uni = der1st->uniform && der1st_sym->uniform && der2nd->uniform && der2nd_sym->uniform;
@@ -2063,13 +2019,7 @@ int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f
 {
     *done = false;
     if ((omega != 0.0 || ushift) && (acc || upd_g)) return 0;
-    static int on = -1;
-    if (on < 0) {
-        const char *names[4] = {"X3D_NO_TILE3", "X3D_XSCAN_P1", "X3D_NO_XSCAN", "X3D_XDIR_GENERIC"};
-        on = 1;
-        for (const char *nm : names) { const char *e = getenv(nm); if (e && e[0] == '1') on = 0; }
-    }
-    if (!on || !x3d_xscan_fast_ok(der1st, der1st_sym, der2nd) || !x3d_xscan_fast_ok(der1st_sym, der1st, der2nd_sym)) return 0;
+    if (!b->sw.x_tq3 || !x3d_xscan_fast_ok(der1st, der1st_sym, der2nd) || !x3d_xscan_fast_ok(der1st_sym, der1st, der2nd_sym)) return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
     const int Q = der1st->tab.Q, np = b->ny * b->nz;
     if (b->nx != 64 * Q || np % 2) return 0;
@@ -2081,9 +2031,7 @@ int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f
         if (!ok(op_s) || !ok(op_i)) return 0;
     }
     const bool narrow = stencil_narrow(der1st) && stencil_narrow(der2nd) && (!upd || (stencil_narrow(op_s) && stencil_narrow(op_i)));
-    static int xcirc = -1;
-    if (xcirc < 0) { const char *e = getenv("X3D_NO_XCIRC"); xcirc = (e && e[0] == '1') ? 0 : 1; }
-    const bool circ = xcirc && circ_env_on() && narrow && der1st->circ_ok && der1st_sym->circ_ok && der2nd->circ_ok && der2nd_sym->circ_ok &&
+    const bool circ = b->sw.x_circ && narrow && der1st->circ_ok && der1st_sym->circ_ok && der2nd->circ_ok && der2nd_sym->circ_ok &&
                       (!upd || (op_s->circ_ok && op_i->circ_ok));
     const size_t lds = circ ? 0 : sizeof(real_t) * 64 * (upd ? 3 * LT_NC(Q) + LT_N(Q) : 2 * LT_N(Q));
     if (lds > 160 * 1024) return 0;
@@ -2133,18 +2081,12 @@ int x3d_xscan_tds_lincomb(x3d_backend *b, real_t *du, const x3d_tdsops *t, real_
                           const real_t *c, const real_t *const *x, const real_t *wall, bool *done)
 {
     *done = false;
-    static int on = -1;
-    if (on < 0) {
-        const char *names[3] = {"X3D_NO_TDS_LINCOMB", "X3D_NO_XSCAN", "X3D_XDIR_GENERIC"};
-        on = 1;
-        for (const char *nm : names) { const char *e = getenv(nm); if (e && e[0] == '1') on = 0; }
-    }
-    if (!on || !xscan_ok(t)) return 0;
+    if (b->sw.no_tds_lincomb || !b->sw.x_fast || !xscan_ok(t)) return 0;
     const int Q = t->tab.Q;
     if (!(t->tab.bulk_only && t->n_tds == 64 * Q && t->tab.n_rhs == t->n_tds && b->nx == 64 * Q)) return 0;
     const int np = b->ny * b->nz;
     const bool narrow = stencil_narrow(t);
-    const bool circ = narrow && t->uniform && t->circ_ok && circ_env_on();  // (the same choice as x3d_xscan_tds: same bits)
+    const bool circ = narrow && t->uniform && t->circ_ok && !b->sw.no_circ;  // (the same choice as x3d_xscan_tds: same bits)
     const size_t lds = circ ? 0 : sizeof(real_t) * LT_N(Q) * 64;
     int blocks = (np + 7) / 8;
     const int cap = circ ? 1024 : 768;

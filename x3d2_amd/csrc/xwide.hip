@@ -516,19 +516,10 @@ __global__ void __launch_bounds__(512)
 }
 
 // ---------------------------------------------------------------- launchers
-static bool wide_env_on()
-{
-    static int on = -1;
-    if (on < 0) {
-        const char *names[3] = {"X3D_NO_XWIDE", "X3D_NO_XSCAN", "X3D_XDIR_GENERIC"};
-        on = 1;
-        for (const char *nm : names) { const char *e = getenv(nm); if (e && e[0] == '1') on = 0; }
-    }
-    return on == 1;
-}
+// X3D_NO_XWIDE=1 (and what turns the wave-per-pencil x kernels off): the generic kernels serve 1024-row pencils
 static bool wide_ok(const x3d_backend *b, const x3d_tdsops *t)
 {
-    return t->tlc != nullptr && t->tab.Q == WQ && t->tab.bulk_only && t->n_tds == 64 * WQ && t->tab.n_rhs == t->n_tds &&
+    return !b->sw.no_xwide && b->sw.x_fast && t->tlc != nullptr && t->tab.Q == WQ && t->tab.bulk_only && t->n_tds == 64 * WQ && t->tab.n_rhs == t->n_tds &&
            b->nx == 64 * WQ;
 }
 static bool wide_narrow(const x3d_tdsops *t)
@@ -536,14 +527,9 @@ static bool wide_narrow(const x3d_tdsops *t)
     return t->coeffs[0] == 0.0 && t->coeffs[1] == 0.0 && t->coeffs[7] == 0.0 && t->coeffs[8] == 0.0;
 }
 // the circulant form of the 1024-row kernels (circ_solve with 16 rows per lane).  X3D_NO_CIRC=1 / X3D_NO_XCIRC=1: not (A/B)
-static bool wide_circ(const x3d_tdsops *t)
+static bool wide_circ(const x3d_backend *b, const x3d_tdsops *t)
 {
-    static int on = -1;
-    if (on < 0) {
-        on = 1;
-        for (const char *nm : {"X3D_NO_CIRC", "X3D_NO_XCIRC"}) { const char *e = getenv(nm); if (e && e[0] == '1') on = 0; }
-    }
-    return on && t->circ_ok && t->uniform && t->tab.Q == 16;
+    return b->sw.x_circ && t->circ_ok && t->uniform && t->tab.Q == 16;
 }
 static XOp wide_xop(const x3d_tdsops *t)
 {
@@ -560,10 +546,10 @@ int x3d_xwide_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops 
     *done = false;
     if (nsum) *nsum = 0;
     if (acc) psum = nullptr;
-    if (!wide_env_on() || !wide_ok(b, t)) return 0;
+    if (!wide_ok(b, t)) return 0;
     const int np = b->ny * b->nz;
     const bool narrow = wide_narrow(t);
-    const bool circ = narrow && wide_circ(t);
+    const bool circ = narrow && wide_circ(b, t);
     const size_t lds = sizeof(real_t) * ((circ ? 0 : LTC_N(WQ)) + 8 * WSTRIP);
     int blocks = (np + 7) / 8;
     // 98 KB of LDS: one 8-wave workgroup per CU; circulant form: 74 KB of strips, two (not with the partial sums: their
@@ -593,11 +579,9 @@ int x3d_xwide_tds_lincomb(x3d_backend *b, real_t *du, const x3d_tdsops *t, real_
                           int *nsum)
 {
     *done = false;
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_TDS_LINCOMB"); on = (e && e[0] == '1') ? 0 : 1; }
-    if (!on || !wide_env_on() || !wide_ok(b, t)) return 0;
+    if (b->sw.no_tds_lincomb || !wide_ok(b, t)) return 0;
     const int np = b->ny * b->nz;
-    const bool circ = wide_narrow(t) && wide_circ(t);  // (the same choice as x3d_xwide_tds: the same bits)
+    const bool circ = wide_narrow(t) && wide_circ(b, t);  // (the same choice as x3d_xwide_tds: the same bits)
     const size_t lds = sizeof(real_t) * ((circ ? 0 : LTC_N(WQ)) + 8 * WSTRIP);
     int blocks = (np + 7) / 8;
     const int cap = (circ && !psum) ? 512 : 256;
@@ -632,15 +616,14 @@ int x3d_xwide_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f
 {
     *done = false;
     if (omega != 0.0 && acc) return 0;
-    if (!wide_env_on() || !wide_ok(b, der1st) || !wide_ok(b, der1st_sym) || !wide_ok(b, der2nd) || !wide_ok(b, der2nd_sym))
+    if (!wide_ok(b, der1st) || !wide_ok(b, der1st_sym) || !wide_ok(b, der2nd) || !wide_ok(b, der2nd_sym))
         return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
     const int np = b->ny * b->nz;
-    static int uni_on = -1;  // X3D_NO_UNIFORM=1: the general tables on uniform grids too (A/B, as for the tile kernels)
-    if (uni_on < 0) { const char *e = getenv("X3D_NO_UNIFORM"); uni_on = (e && e[0] == '1') ? 0 : 1; }
-    const bool uni = uni_on && der1st->uniform && der1st_sym->uniform && der2nd->uniform && der2nd_sym->uniform;
+    // X3D_NO_UNIFORM=1: the general tables on uniform grids too (A/B, as for the tile kernels)
+    const bool uni = !b->sw.no_uniform && der1st->uniform && der1st_sym->uniform && der2nd->uniform && der2nd_sym->uniform;
     const bool narrow = wide_narrow(der1st) && wide_narrow(der2nd);
-    const bool circ = uni && narrow && wide_circ(der1st) && wide_circ(der1st_sym) && wide_circ(der2nd) && wide_circ(der2nd_sym);
+    const bool circ = uni && narrow && wide_circ(b, der1st) && wide_circ(b, der1st_sym) && wide_circ(b, der2nd) && wide_circ(b, der2nd_sym);
     const size_t lds = sizeof(real_t) * ((circ ? 0 : 2 * (uni ? LTU_N : LTC_N(WQ))) + 8 * WSTRIP);
     const int blocks = x3d_persistent_blocks(b, (np + 7) / 8);
     const Circ4 c4{{der1st->circ, der2nd->circ, der1st->circ, der1st->circ}};
@@ -678,17 +661,15 @@ int x3d_xwide_transeq3_upd(x3d_backend *b, real_t *const r[3], real_t *const f[3
                            real_t omega, const real_t *ushift, bool *done)
 {
     *done = false;
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_XWIDE_UPD"); on = (e && e[0] == '1') ? 0 : 1; }
     const x3d_tdsops *ops[6] = {der1st, der1st_sym, der2nd, der2nd_sym, op_s, op_i};
-    if (!on || !wide_env_on()) return 0;
+    if (b->sw.no_xwide_upd) return 0;
     for (const x3d_tdsops *t : ops)
         if (!wide_ok(b, t) || !t->uniform) return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
     const int np = b->ny * b->nz;
     const bool narrow = wide_narrow(der1st) && wide_narrow(der2nd) && wide_narrow(op_s) && wide_narrow(op_i);
     bool circ = narrow;
-    for (const x3d_tdsops *t : ops) circ = circ && wide_circ(t);
+    for (const x3d_tdsops *t : ops) circ = circ && wide_circ(b, t);
     const size_t lds = sizeof(real_t) * ((circ ? 0 : 4 * LTU_N) + 8 * WSTRIP);
     if (lds > 160 * 1024) return 0;
     const int blocks = x3d_persistent_blocks(b, (np + 7) / 8);

@@ -462,9 +462,7 @@ int x3d_y010_run(x3d_backend *b, real2_t *c, int nxs, int nx, int ny, int nz, in
     g.lu0 = lu ? lu[0] : nullptr; g.lu1 = lu ? lu[1] : nullptr;
     g.nxs = nxs; g.nz = nz; g.nx = nx; g.sym = sym;
     g.nzl = nzl > 0 ? nzl : nz;
-    static int nodb = -1;
-    if (nodb < 0) { const char *e = getenv("X3D_Y010_NO_DB"); nodb = (e && e[0] == '1') ? 1 : 0; }
-    g.db = nodb ? 0 : 1;
+    g.db = b->sw.y010_no_db ? 0 : 1;
     const size_t lds = sizeof(real2_t) * (8 * Y010_P + 256) + sizeof(real_t) * (mode == 3 ? 2 * Y010_LD : (mode == 4 ? 3 * Y010_LH : 0));
     const dim3 grid((unsigned)((size_t)g.nzl * (nxs / 8)));
 #define GO(M_)                                                                                          \

@@ -428,16 +428,6 @@ __global__ void __launch_bounds__(64 * NP, NP == 8 ? 4 : 1)
 }
 
 // ---------------------------------------------------------------- launchers
-static bool gen_env_on()
-{
-    static int on = -1;
-    if (on < 0) {
-        const char *names[4] = {"X3D_NO_YGEN", "X3D_NO_YTILE", "X3D_NO_XSCAN", "X3D_NO_VIA_X"};
-        on = 1;
-        for (const char *nm : names) { const char *e = getenv(nm); if (e && e[0] == '1') on = 0; }
-    }
-    return on == 1;
-}
 static bool gen_ok(const x3d_backend *b, int dir, const x3d_tdsops *t, int Q)
 {
     const int n = dir == X3D_DIR_Y ? b->ny : b->nz;
@@ -449,10 +439,8 @@ static bool gen_ok(const x3d_backend *b, int dir, const x3d_tdsops *t, int Q)
 // pencils: 52 of 64 lanes busy instead of 43), else the operators' own Q.  X3D_NO_Q5=1: always the latter (A/B)
 static int gen_q(const x3d_backend *b, int dir, const x3d_tdsops *const *ops, int nops)
 {
-    static int q5 = -1;
-    if (q5 < 0) { const char *e = getenv("X3D_NO_Q5"); q5 = (e && e[0] == '1') ? 0 : 1; }
     const int n = dir == X3D_DIR_Y ? b->ny : b->nz;
-    bool all5 = q5 && n <= 320;
+    bool all5 = !b->sw.no_q5 && n <= 320;
     for (int k = 0; k < nops; k++) all5 = all5 && ops[k]->tl5 != nullptr;
     return all5 ? 5 : ops[0]->tab.Q;
 }
@@ -463,11 +451,9 @@ static XOp gen_xop(const x3d_tdsops *t, int Q, bool direct = false)
     return o;
 }
 // the DIRECT form (thomas_solve) where every operator of the launch offers its tables.  X3D_NO_DIRECT=1: never (A/B)
-static bool gen_direct(const x3d_tdsops *const *ops, int nops, int Q)
+static bool gen_direct(const x3d_backend *b, const x3d_tdsops *const *ops, int nops, int Q)
 {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("X3D_NO_DIRECT"); on = (e && e[0] == '1') ? 0 : 1; }
-    bool d = on && Q == 5;
+    bool d = !b->sw.no_direct && Q == 5;
     for (int k = 0; k < nops; k++) d = d && ops[k]->direct && ops[k]->td5 != nullptr;
     return d;
 }
@@ -493,11 +479,11 @@ int x3d_ygen_pair(x3d_backend *b, int dir, int mode, real_t *out1, real_t *out2,
                   const x3d_tdsops *ta, const x3d_tdsops *tb, bool *done)
 {
     *done = false;
-    if (!gen_env_on() || dir == X3D_DIR_X) return 0;
+    if (!b->sw.ygen || dir == X3D_DIR_X) return 0;
     const x3d_tdsops *const ops[2] = {ta, mode == 2 ? ta : tb};
     const int Q = gen_q(b, dir, ops, 2);
     if (!gen_ok(b, dir, ta, Q) || (mode != 2 && !gen_ok(b, dir, tb, Q))) return 0;
-    const bool direct = gen_direct(ops, 2, Q);
+    const bool direct = gen_direct(b, ops, 2, Q);
     const size_t lds = sizeof(real_t) * ((size_t)(mode == 2 ? 1 : 2) * (direct ? DT_NC(Q) : LT_N(Q)) * 64 + 16 * (64 * Q + 10) + 2 * CS_N(Q));
     if (lds > 160 * 1024) return 0;
     const GenLaunch g = gen_launch(b, dir);
@@ -532,7 +518,7 @@ int x3d_ygen_transeq3(x3d_backend *b, int dir, real_t *const r[3], const real_t 
                       const x3d_tdsops *der2nd_sym, int acc, bool *done)
 {
     *done = false;
-    if (!gen_env_on() || dir == X3D_DIR_X) return 0;
+    if (!b->sw.ygen || dir == X3D_DIR_X) return 0;
     const x3d_tdsops *const ops[4] = {der1st, der1st_sym, der2nd, der2nd_sym};
     const int Q = gen_q(b, dir, ops, 4);
     if (!gen_ok(b, dir, der1st, Q) || !gen_ok(b, dir, der1st_sym, Q) || !gen_ok(b, dir, der2nd, Q) ||
@@ -544,7 +530,7 @@ int x3d_ygen_transeq3(x3d_backend *b, int dir, real_t *const r[3], const real_t 
     // 8 pencils per workgroup, two workgroups per CU: 257..320-row pencils (Q = 5), nx a multiple of 32 (tile pairs share
     // 128-byte lines and must not straddle rows of tiles)
     const int NP = (Q == 5 && b->nx % 32 == 0) ? 8 : 16;
-    const bool direct = gen_direct(ops, 4, Q);
+    const bool direct = gen_direct(b, ops, 4, Q);
     const size_t lds = sizeof(real_t) * ((size_t)(direct ? DT_NC(Q) + DT_N(Q) : LT_NC(Q) + LT_N(Q)) * 64 + NP * (64 * Q + 10) + 2 * CS_N(Q));
     if (lds > 160 * 1024) return 0;
     GenLaunch g = gen_launch(b, dir);

@@ -191,25 +191,11 @@ static int fft1024_init()
     X3D_HIP(hipMemcpy(g_tw1024, h.data(), sizeof(real2_t) * 512, hipMemcpyHostToDevice));
     return 0;
 }
-static bool zfirst010_off()
-{
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("X3D_NO_ZFIRST010"); off = (e && e[0] == '1') ? 1 : 0; }
-    return off != 0;
-}
 static bool zfirst010_sizes(const x3d_poisson *p)
 {
     const x3d_backend *b = p->b;
     return p->stretched && p->luz[0] && (!p->sym || p->luz[1]) && p->nx == 1024 && p->ny == 256 && p->nz == 512 &&
            b->nx == 1024 && b->nz == 512 && b->ny >= 256 && p->c_elems >= (size_t)257 * 256 * ZH010_PX;
-}
-
-// X3D_NO_ZFIRST=1, read ONCE per process (both functions below ask here)
-static bool zfirst_off()
-{
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("X3D_NO_ZFIRST"); off = (e && e[0] == '1') ? 1 : 0; }
-    return off != 0;
 }
 
 // the z-first solve is on offer for this solver (X3D_NO_ZFIRST=1: never); builds the reciprocal wave numbers on first use
@@ -219,11 +205,11 @@ int x3d_zfirst_arg(x3d_poisson *p, ZfArg *out, bool *ok)
     if (p->ext_middle) {  // a proxy (the shim's y-slab solve): the spectrum is the slab solver's
         if (int rc = x3d_fft512_init()) return rc;
         if (out) *out = ZfArg{p->ext_c, x3d_fft512_twiddles(), p->ext_ny, p->ext_px, 0};
-        *ok = !zfirst_off();
+        *ok = !p->b->sw.no_zfirst;
         return 0;
     }
-    if (zfirst_off()) return 0;
-    if (!zfirst010_off() && zfirst010_sizes(p)) {  // the channel's 010 solve
+    if (p->b->sw.no_zfirst) return 0;
+    if (!p->b->sw.no_zfirst010 && zfirst010_sizes(p)) {  // the channel's 010 solve
         if (int rc = x3d_fft512_init()) return rc;
         if (int rc = fft1024_init()) return rc;
         if (out) *out = ZfArg{p->c, x3d_fft512_twiddles(), p->ny, (long)ZH010_PX, p->ny};
@@ -244,7 +230,7 @@ int x3d_zfirst_arg(x3d_poisson *p, ZfArg *out, bool *ok)
 // (for the deferred-execution layer's rewrite: no side effects)
 bool x3d_zfirst_on_offer(x3d_poisson *p)
 {
-    return p && !zfirst_off() && (p->ext_middle != nullptr || zfirst_sizes(p));
+    return p && !p->b->sw.no_zfirst && (p->ext_middle != nullptr || zfirst_sizes(p));
 }
 
 extern "C" int x3d_poisson_zfirst_ok(x3d_poisson *p, int *ok)

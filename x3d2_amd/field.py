@@ -4,11 +4,11 @@ equally sized device blocks handed out with a direction tag and a data_loc.
 
 Blocks are torch CUDA tensors (PyTorch is the device-memory plumbing); the
 kernels only ever see their raw pointers."""
-import os
 
 import torch
 
 from . import _lib
+from .switches import Switches
 from .common import DIR_C, DIR_X, DIR_Y, DIR_Z, NULL_LOC, X3dError
 
 
@@ -42,14 +42,15 @@ class Allocator:
     """allocator_t: LIFO free list, blocks are never freed before destroy
     (src/allocator.f90:113-179)."""
 
-    def __init__(self, nblock_elems, device):
+    def __init__(self, nblock_elems, device, sw=None):
         self.n = int(nblock_elems)
         self.device = device
         self.free = []
         self.next_id = 0
         self.lazy = None  # (lib, backend handle) while the library's deferred execution is on (HipBackend(lazy=True))
         self._registered = []  # tensors whose memory the deferred-execution layer knows as blocks (kept alive)
-        self.stagger = int(os.environ.get("X3D_BLOCK_STAGGER", str(self.STAGGER)))  # (read once)
+        sw = Switches.from_env() if sw is None else sw  # (HipBackend passes its own snapshot)
+        self.stagger = self.STAGGER if sw.block_stagger is None else sw.block_stagger
 
     # Blocks start 4224 B (one padded row of a 512^3 block) further into their allocation than the previous one,
     # modulo 16: the kernels stream 4-12 blocks at the same relative offset at once, and with every block on a

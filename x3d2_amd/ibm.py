@@ -10,12 +10,12 @@ calls -- as the A/B and test baseline.
 The reference reads iibm and ep1 from `ibm_XYZ.bp`, an ADIOS2 file written by an outside tool; here the same two
 variables travel in an .npz file (`Ibm.save` / `Ibm.from_file`)."""
 import ctypes
-import os
 
 import numpy as np
 
 from . import _lib
 from .common import DIR_X, VERT, X3dError
+from .switches import Switches
 
 IIBM_BASIC = 1  # iibm_basic, src/module/ibm.f90:25
 
@@ -67,7 +67,7 @@ class Ibm:
         self.ep1 = np.ascontiguousarray(ep1, dtype=np.float64)
         if self.ep1.shape != (nz, ny, nx):
             raise X3dError(f"Ibm: ep1 has shape {self.ep1.shape}, this rank's vertices are {(nz, ny, nx)}")
-        self.sparse = os.environ.get("X3D_NO_IBM_SPARSE") != "1"
+        self.sparse = not Switches.from_env().no_ibm_sparse
         if self.iibm != IIBM_BASIC:
             return
         a = np.ascontiguousarray(self.ep1, dtype=_lib.NP_REAL)

@@ -9,10 +9,11 @@ direction; the py or pz peers of a transpose), batched into one group
 (batch_isend_irecv = ncclGroupStart/End) -- no bulk collective on the data path.
 With the "gloo" backend (CPU tests, or several ranks sharing one GPU in the
 GPU parity tests) device buffers are staged through host memory."""
-import os
 
 import torch
 import torch.distributed as dist
+
+from .switches import Switches
 
 
 class _Done:
@@ -54,6 +55,7 @@ class Comm:
     _verdicts = {}
 
     def __init__(self, group=None, self_check=True):
+        sw = self.sw = Switches.from_env()  # (a Comm is built before, and without, a backend: its own snapshot)
         self.enabled = dist.is_available() and dist.is_initialized()
         self.group = group
         self.rank = dist.get_rank(group) if self.enabled else 0
@@ -62,7 +64,7 @@ class Comm:
         self.host_staged = self.backend == "gloo"
         # exchanges started on a second HIP stream overlap with kernels of the compute stream that do not
         # depend on them (X3D_NO_OVERLAP=1: every exchange is ordered on the compute stream, for A/B runs)
-        self.overlap = os.environ.get("X3D_NO_OVERLAP") != "1"
+        self.overlap = not sw.no_overlap
         self._cstream = None
         self._cycles_per_s = None
         self.stream_probe = None  # ms of each candidate's probe (_pick_stream), None until a stream was needed
@@ -71,19 +73,19 @@ class Comm:
         # X3D_COMM_SELF_VIA_NCCL=1 (one GPU, world size 1, X3D_EMULATE_DECOMP): exchanges with THIS rank go through
         # RCCL send / recv to itself instead of device copies -- the only way to put the RCCL code path (group launch,
         # communication stream, wait semantics) under a test on a one-GPU box
-        self.self_via_nccl = self.enabled and self.backend == "nccl" and os.environ.get("X3D_COMM_SELF_VIA_NCCL") == "1"
+        self.self_via_nccl = self.enabled and self.backend == "nccl" and sw.comm_self_via_nccl
         # X3D_COMM_FAKE_PEERS=1 (world size 1 only): EVERY peer of an all-to-all is this rank -- chunk i of the send buffer
         # lands in slot i of the receive buffer, as a device copy or (with X3D_COMM_SELF_VIA_NCCL) as N send / recv pairs
         # to self in one RCCL group: the group sizes, chunk lengths and part pipelining of an N-rank all-to-all run through
         # RCCL on a one-GPU box (the numbers mean nothing: tests compare the two transports bit for bit)
-        self.fake_peers = self.size == 1 and os.environ.get("X3D_COMM_FAKE_PEERS") == "1"
+        self.fake_peers = self.size == 1 and sw.comm_fake_peers
         # X3D_COMM_EMULATE_LINKS=<GB/s per link and direction> (world size 1, exchanges through RCCL to self): every
         # exchange additionally holds its stream for the time the message would spend on xGMI links of that rate -- an
         # all-to-all among n peers sends 1 / n of its bytes over each of n - 1 links at once (bytes / n / rate), a
         # neighbour exchange its two messages over two links at once (largest message / rate) -- so that a one-GPU box
         # shows which part of the transfers a schedule hides (bench.py --virtual-ranks; a timeline, not a measurement of links)
         self.link_rate = None
-        e = os.environ.get("X3D_COMM_EMULATE_LINKS")
+        e = sw.comm_emulate_links
         if e and self.size == 1:
             self.link_rate = float(e) * 1e9
             # with the links emulated a message to self moves as a device copy on the communication stream (RCCL's
@@ -91,7 +93,7 @@ class Comm:
             # time); every group additionally holds the stream X3D_COMM_EMULATE_LATENCY_US (default 30: what one RCCL
             # point-to-point group costs to launch on this pool, profiles/r05_*) -- the RCCL calls themselves stay under
             # test in the bit-for-bit RCCL-to-self tests, which run without the emulation
-            self.link_latency = float(os.environ.get("X3D_COMM_EMULATE_LATENCY_US", "30")) * 1e-6
+            self.link_latency = sw.comm_emulate_latency_us * 1e-6
         self._checked = self.host_staged or not self.enabled or not self.overlap or \
             (self.size == 1 and not self.self_via_nccl)
         self.self_check_result = None
@@ -207,7 +209,7 @@ class Comm:
         colliding one is kept referenced (the pool then hands out the next) and passed over."""
         import time
         self.stream_probe = []
-        if os.environ.get("X3D_COMM_NO_STREAM_PROBE") == "1":
+        if self.sw.comm_no_stream_probe:
             return torch.cuda.Stream()
         n = int(2e-3 * self._sleep_cycles_per_s())
 

@@ -5,7 +5,6 @@ backend supplies (fft_forward / fft_postprocess_000 / fft_backward through
 rocFFT; reference CPU hooks: src/backend/omp/poisson_fft.f90:89-137)."""
 import ctypes
 import math
-import os
 
 import numpy as np
 
@@ -179,14 +178,15 @@ def stretching_matrix_zfirst(pf, mesh, xd, yd, zd, eys, exs, ezs):
 def make_poisson_fft(backend, mesh, xdirps, ydirps, zdirps):
     """init_poisson_fft: single-rank 3-D rocFFT plan, or the pencil-decomposed
     solver when the domain is split over ranks"""
-    force = os.environ.get("X3D_FORCE_PENCIL_FFT")  # "1": generic pencil solver, "slab": z slabs, "yslab": y slabs
+    sw = backend.sw
+    force = sw.force_pencil_fft  # "1": generic pencil solver, "slab": z slabs, "yslab": y slabs
     if mesh.nproc > 1 or force in ("1", "slab", "yslab"):
         ny = int(mesh.get_global_dims(CELL)[1])
         pz = int(mesh.nproc_dir[2])
         py = int(mesh.nproc_dir[1])
         yslab_ok = (pz == 1 and py in (1, 2, 4, 8) and all(mesh.periodic_BC) and force in (None, "yslab")
                     and tuple(int(v) for v in mesh.get_dims(CELL)) == (512, 512, 512)
-                    and os.environ.get("X3D_NO_YSLAB_FFT") != "1")
+                    and not sw.no_yslab_fft)
         if yslab_ok and (py > 1 or force == "yslab"):
             # y slabs of 512^3 cells: z is whole on every rank, the z-first solve applies (csrc/sfftz.hip)
             return HipSlabPoissonFFTZ(backend, mesh, xdirps, ydirps, zdirps)
@@ -194,7 +194,7 @@ def make_poisson_fft(backend, mesh, xdirps, ydirps, zdirps):
             # non-periodic y on z slabs (the channel case): the x modes are split over the ranks, y stays whole
             return HipSlabPoissonFFT010(backend, mesh, xdirps, ydirps, zdirps)
         slab_ok = (int(mesh.nproc_dir[1]) == 1 and ny == 512 and 512 % pz == 0 and all(mesh.periodic_BC)
-                   and os.environ.get("X3D_NO_SLAB_FFT") != "1")
+                   and not sw.no_slab_fft)
         if slab_ok and force != "1":
             return HipSlabPoissonFFT(backend, mesh, xdirps, ydirps, zdirps)
         return HipPencilPoissonFFT(backend, mesh, xdirps, ydirps, zdirps)
@@ -275,7 +275,7 @@ class HipPoissonFFT:
             # the channel's sizes on one rank: the operators once more in the z-first layout (x3d_poisson_zfirst_ok then
             # offers the solve with its z transforms on the tiles of the neighbouring z operator pairs, csrc/zfirst.hip)
             if (type(self) is HipPoissonFFT and (self.nx_glob, self.ny_glob, self.nz_glob) == (1024, 256, 512)
-                    and os.environ.get("X3D_NO_ZFIRST010") != "1" and os.environ.get("X3D_NO_ZFIRST") != "1"
+                    and not backend.lib_switch("X3D_NO_ZFIRST010") and not backend.lib_switch("X3D_NO_ZFIRST")
                     and not getattr(backend, "lazy", False)):
                 z0, z1 = stretching_matrix_zfirst(self, mesh, *self._dirps, *self._es)
                 _lib.check(backend.lib.x3d_poisson_set_stretching_zfirst(self.h, int(self.stretched_y_sym), dp(z0), dp(z1)))
@@ -568,7 +568,7 @@ class HipPencilPoissonFFT(HipPoissonFFT):
         h = VP()
         _lib.check(backend.lib.x3d_pfft_create_parts(
             backend.h, ctypes.byref(h), _lib.ints(self.nx_glob, self.ny_glob, self.nz_glob), self.py, self.pz,
-            self.ry, self.rz, int(os.environ.get("X3D_PENCIL_PARTS", "0"))))
+            self.ry, self.rz, backend.sw.pencil_parts))
         self.h = h
         sz = (ctypes.c_long * 8)()
         _lib.check(backend.lib.x3d_pfft_sizes(h, sz))
@@ -724,7 +724,7 @@ class HipSlabPoissonFFT(HipPoissonFFT):
         backend, mesh = self.backend, self.mesh
         self.pz, self.rz = int(mesh.nproc_dir[2]), int(mesh.nrank_dir[2])
         ys = self.ny_glob // self.pz
-        parts = int(os.environ.get("X3D_SLAB_PARTS", "4"))
+        parts = 4 if backend.sw.slab_parts is None else backend.sw.slab_parts
         while parts > 1 and ys % parts:
             parts -= 1
         self.parts = max(parts, 1)
@@ -748,7 +748,7 @@ class HipSlabPoissonFFT(HipPoissonFFT):
         self.sbuf = torch.zeros(n, dtype=_lib.torch_real(), device=backend.device)
         # X3D_EMULATE_ALIAS=1 (one process standing in for an N > 1 run): the "all-to-all with itself" needs no copy when
         # the receive buffer IS the send buffer -- what is left is exactly the kernels an N > 1 run adds
-        alias = self.pz == 1 and os.environ.get("X3D_EMULATE_ALIAS") == "1"
+        alias = self.pz == 1 and backend.sw.emulate_alias
         self.rbuf = self.sbuf if alias else torch.zeros(n, dtype=_lib.torch_real(), device=backend.device)
         npy = int(mesh.nproc_dir[1])
         ry = int(mesh.nrank_dir[1])
@@ -828,7 +828,7 @@ class HipSlabPoissonFFTZ(HipPoissonFFT):
         import torch
         backend, mesh = self.backend, self.mesh
         self.py, self.ry = int(mesh.nproc_dir[1]), int(mesh.nrank_dir[1])
-        parts = int(os.environ.get("X3D_SLAB_PARTS", "0"))
+        parts = backend.sw.slab_parts or 0
         h = VP()
         _lib.check(backend.lib.x3d_sfftz_create(
             backend.h, ctypes.byref(h), _lib.ints(self.nx_glob, self.ny_glob, self.nz_glob), self.py, self.ry, parts))
@@ -849,18 +849,18 @@ class HipSlabPoissonFFTZ(HipPoissonFFT):
         _lib.check(backend.lib.x3d_sfftz_set_waves(h, *[a.ctypes.data_as(_lib.c_double_p) for a in self._keep]))
         self._keep = None
         self.sbuf = torch.zeros(2 * nbuf, dtype=_lib.torch_real(), device=backend.device)
-        alias = self.py == 1 and os.environ.get("X3D_EMULATE_ALIAS") == "1"
+        alias = self.py == 1 and backend.sw.emulate_alias
         self.rbuf = self.sbuf if alias else torch.zeros(2 * nbuf, dtype=_lib.torch_real(), device=backend.device)
         self.peers = [r for r in range(self.py)]  # rank = ry (x and z undivided)
         self.poisson = self.poisson_000
         # round 5: groups of local y rows x groups of kz planes (csrc/sfftz.hip, "BLOCKS"): X3D_SLAB_YPARTS groups of
         # rows (default 4 on several ranks, 1 in a single process; 1 = rounds 3-4's schedule, kz groups only)
-        yp = int(os.environ.get("X3D_SLAB_YPARTS", "0"))
+        yp = backend.sw.slab_yparts
         self.yparts = yp if yp > 0 else (4 if self.py > 1 else 1)
         if 512 % self.yparts:
             raise X3dError("X3D_SLAB_YPARTS must divide 512")
         self.rows = [(a * (512 // self.yparts), 512 // self.yparts) for a in range(self.yparts)]
-        rs = os.environ.get("X3D_SLAB_ROWS")  # uneven groups, e.g. "64,160,160,128": a small first group fills the pipeline
+        rs = backend.sw.slab_rows  #           uneven groups, e.g. "64,160,160,128": a small first group fills the pipeline
         if rs:                                 # sooner, a small last one drains it sooner
             cnt = [int(v) for v in rs.split(",")]
             if sum(cnt) != 512 or min(cnt) <= 0:
@@ -902,7 +902,7 @@ class HipSlabPoissonFFTZ(HipPoissonFFT):
         (X3D_SLAB_SCHEDULE=blocks: every (a, m) block its own group, 2 A K)."""
         lib, h, sb, rb = self.backend.lib, self.h, self.sbuf, self.rbuf
         A, K = self.yparts, self.parts
-        every = os.environ.get("X3D_SLAB_SCHEDULE") == "blocks"
+        every = self.backend.sw.slab_schedule == "blocks"
         there = []
         for a, (y0, nyr) in enumerate(self.rows):
             front(a, y0, nyr)
@@ -918,7 +918,8 @@ class HipSlabPoissonFFTZ(HipPoissonFFT):
         # stages complete.  Default T = K: the whole way back is rows-major -- the y stages have run beside the forward
         # transfers anyway, and the z pairs (1.2 ms per solve at 8 ranks) then overlap all of the transfers instead of the
         # last kz group's only (8 emulated ranks: T = 1 57.8, 2 56.1, 3 55.0, 4 54.7 ms per step; X3D_SLAB_TAIL)
-        T = K if every else max(1, min(K, int(os.environ.get("X3D_SLAB_TAIL", str(K)))))
+        tail = self.backend.sw.slab_tail
+        T = K if every or tail is None else max(1, min(K, tail))
         for m in range(K):
             for k, hnd in there:
                 if k is None or k == m:
@@ -1061,7 +1062,9 @@ class HipSlabPoissonFFT010(HipPoissonFFT):
         h = VP()
         # the rank's columns travel in groups (overlap of the transfers with the z stage and the pentadiagonal solves);
         # X3D_SLAB_PARTS: how many (0 = the library's choice; default: that on several ranks, 1 in a single process)
-        parts = int(__import__("os").environ.get("X3D_SLAB_PARTS", "0" if self.pz > 1 else "1"))
+        parts = backend.sw.slab_parts
+        if parts is None:
+            parts = 0 if self.pz > 1 else 1
         _lib.check(backend.lib.x3d_sfft010_create_parts(
             backend.h, ctypes.byref(h), _lib.ints(self.nx_glob, self.ny_glob, self.nz_glob), self.pz, self.rz, parts))
         self.h = h
@@ -1091,7 +1094,7 @@ class HipSlabPoissonFFT010(HipPoissonFFT):
                 self.a_odd = self.a_even = self.a_full = None
         n = 2 * self.pz * self.chunk
         self.sbuf = torch.zeros(n, dtype=_lib.torch_real(), device=backend.device)
-        alias = self.pz == 1 and __import__("os").environ.get("X3D_EMULATE_ALIAS") == "1"  # (see HipSlabPoissonFFT)
+        alias = self.pz == 1 and backend.sw.emulate_alias  # (see HipSlabPoissonFFT)
         self.rbuf = self.sbuf if alias else torch.zeros(n, dtype=_lib.torch_real(), device=backend.device)
         self.peers = [r for r in range(self.pz)]  # (x and y undivided: rank = rz)
         self.poisson = self.poisson_010
@@ -1164,7 +1167,7 @@ class HipSlabPoissonFFT010(HipPoissonFFT):
     def interleaved_rows(self):
         """as HipPoissonFFT.interleaved_rows; the caller's z operators are then the halo forms
         (HipBackend.tds_tile_ok / tds_halo_main / tds_halo_finish with yperm)"""
-        return self.ny_glob if self.ny_glob % 2 == 0 and os.environ.get("X3D_NO_YPERM") != "1" else 0
+        return self.ny_glob if self.ny_glob % 2 == 0 and not self.backend.sw.no_yperm else 0
 
     def solve_interleaved(self, f):
         self._solve_rows_interleaved(f)

@@ -1,7 +1,6 @@
 """solver_t mirror (/root/reference/src/solver.f90): the "Incompact3D
 algorithm" sequencing -- transeq -> time integrator -> pressure correction --
 over the backend's operator interface.  No arithmetic on field data here."""
-import os
 import numpy as np
 
 from .common import (BC_DIRICHLET, BC_NEUMANN, CELL, DIR_C, DIR_X, DIR_Y, DIR_Z, RDR_C2Z, RDR_X2Y, RDR_X2Z,
@@ -68,6 +67,7 @@ class Solver:
         """src/solver.f90:110-212"""
         cfg = cfg or SolverConfig()
         self.backend, self.mesh, self.cfg = backend, mesh, cfg
+        self.sw = backend.sw  # (the switches as the backend's constructor found them: no step reads the environment)
         self.xdirps, self.ydirps, self.zdirps = Dirps(DIR_X), Dirps(DIR_Y), Dirps(DIR_Z)
         self.vector_calculus = VectorCalculus(backend)
         al = backend.allocator
@@ -108,7 +108,7 @@ class Solver:
         # not read back) and the last (it is not even stored); a middle stage saves a launch only -- same-box A/B at
         # 512^3 RK3, ms per step: none 43.1-43.4, {1} 42.0, {3} 41.7-41.9, {1,3} 41.4-41.6, {1,2,3} 41.3-41.5
         ns = self.time_integrator.nstage
-        e = os.environ.get("X3D_EPI3_STAGES")
+        e = self.sw.epi3_stages
         self._epi3_stages = {int(v) for v in e.split(",")} if e else set(range(1, ns + 1))
         self.n_epi3 = 0
         self.rot_request, self.rot_applied = 0.0, False  # rotation forcing handed to transeq_x (transeq_fused)
@@ -284,7 +284,7 @@ class Solver:
             # taken of the uncorrected u, BaseCase.correction_deferrable)
             g, self.pending_grad = self.pending_grad, None
             if rot != 0.0 or shift is not None:
-                if os.environ.get("X3D_NO_ROT_FUSED") != "1" and \
+                if not self.sw.no_rot_fused and \
                         b.transeq_x_update_rot(du, dv, dw, u, v, w, self.nu, x, g, x.stagder_p2v, x.interpl_p2v, -1.0, rot, shift):
                     served = True
                     if rot != 0.0:
@@ -298,7 +298,7 @@ class Solver:
                 b.allocator.release_block(f)
         if served:
             pass
-        elif (rot != 0.0 or shift is not None) and os.environ.get("X3D_NO_ROT_FUSED") != "1" and \
+        elif (rot != 0.0 or shift is not None) and not self.sw.no_rot_fused and \
                 b.transeq_x_rot(du, dv, dw, u, v, w, self.nu, self.xdirps, rot, shift):
             if rot != 0.0:
                 self.rot_applied = True  # (ChannelCase.forcings: nothing left to do)
@@ -321,7 +321,7 @@ class Solver:
         ti = self.time_integrator
         # (a rotation forcing the x kernel did not take is applied by the case's forcings() to the complete derivatives)
         defer = defer and not (rot != 0.0 and not self.rot_applied)
-        if (defer and os.environ.get("X3D_NO_DEFER") != "1" and os.environ.get("X3D_NO_EPI3") != "1"
+        if (defer and not self.sw.no_defer and not self.sw.no_epi3
                 and not b._decomposed(DIR_Z) and self.nspecies == 0
                 and ti.istage in self._epi3_stages and b.transeq_stage_ok(DIR_Z, self.zdirps)):
             # round 5: the z launch of the three components also does the RK stage of u, v, w (k_ytile_transeq3<EPI>,
@@ -330,9 +330,9 @@ class Solver:
             for f in rhs[:3]:
                 f.set_data_loc(u.data_loc)
             return pending
-        if defer and os.environ.get("X3D_NO_DEFER") != "1" and not b._decomposed(DIR_Z):
+        if defer and not self.sw.no_defer and not b._decomposed(DIR_Z):
             if b.transeq_stage_ok(DIR_Z, self.zdirps):
-                if os.environ.get("X3D_STAGE_IN_TILE") != "1":
+                if not self.sw.stage_in_tile:
                     # default: tile kernel (accumulating) + plain lincomb; the stage inside the tile kernel saves
                     # one read of d* but runs its extra streams at the tile pattern's rate: 59.15 vs 59.4 ms per
                     # step at 512^3 (same-box A/B) -- opt-in
@@ -522,7 +522,7 @@ class Solver:
         """velocity correction from (a1, a2, t1) = (dpdx_sx, dpdy_sx, dpdz_sx) -- the last x operators of gradient_c2v"""
         al = self.backend.allocator
         t1, t2, t3, a1, a2 = blocks
-        if (defer_grad and os.environ.get("X3D_NO_DEFER") != "1" and os.environ.get("X3D_NO_DEFER_GRAD") != "1"
+        if (defer_grad and not self.sw.no_defer and not self.sw.no_defer_grad
                 and self.nspecies == 0):
             # the next sub-step's transeq_x applies the correction inside its own kernel (transeq_fused)
             self.pending_grad = (a1, a2, t1)
