@@ -550,6 +550,24 @@ int x3d_poisson_zfirst_middle(x3d_poisson *p);
 int x3d_poisson_zfirst_forward(x3d_poisson *p, const x3d_real *f_in);
 int x3d_poisson_zfirst_backward(x3d_poisson *p, x3d_real *f_out);
 int x3d_poisson_solve_000_zfirst(x3d_poisson *p, x3d_real *f);
+/* round 7: the solve's forward x transform inside the x operators of divergence_v2c (src/vector_calculus.f90:160-175).
+ * Between those operators and the spectral division everything acts on each x column on its own, with coefficients that do
+ * not depend on x, and the division's multiplier is real and even in every wave number: the transform commutes with all of
+ * it.  x3d_tds_solve_xfft = x3d_tds_solve along x whose result r[0 .. 511] of every pencil leaves as F = rfft(r)
+ * (unnormalised, forward e^{-i}) in 512 reals, "packed half-complex": column 0 = Re F_0, column 1 = Re F_256, columns 2k,
+ * 2k + 1 = Re F_k, Im F_k (k = 1 .. 255); pad columns untouched.  The y and z operators run unchanged on such blocks,
+ * x3d_tds_pair_zfirst mode 0 leaves their z transform in the spectrum, and x3d_poisson_zfirst_middle_xpacked does the
+ * rest: y forward + division (reciprocal wave numbers of the packed columns' x modes) + y inverse ; untangle + x inverse.
+ * The spectrum is then what x3d_poisson_zfirst_middle leaves, up to rounding: 4.5 passes over it instead of 6.5.
+ *   x3d_tds_solve_xfft_ok   *ok = 1: this operator's pencils are ones the kernel takes (512 rows, uniform periodic)
+ *   x3d_poisson_xfft_ok     *ok = 1: the 512^3 000 z-first solve is on offer for p and X3D_NO_XFFT_DIV is not 1
+ *   x3d_c2c512_x_rows       the solve's x passes on rows of the caller's: mode -1 forward, +1 inverse, +2 the inverse of
+ *                           rows packed half-complex along x (nrows rows of 512 complex numbers, pitch complex apart) */
+int x3d_tds_solve_xfft_ok(x3d_backend *b, const x3d_tdsops *t, int *ok);
+int x3d_tds_solve_xfft(x3d_backend *b, x3d_real *du, const x3d_real *u, const x3d_tdsops *t);
+int x3d_poisson_xfft_ok(x3d_poisson *p, int *ok);
+int x3d_poisson_zfirst_middle_xpacked(x3d_poisson *p);
+int x3d_c2c512_x_rows(x3d_backend *b, x3d_real *c, long nrows, long pitch, int mode);
 /* round 6: the same reordering for the channel's solve -- poisson_010 (src/poisson_fft.f90:228-242) on a stretched y with
  * 256 cell rows, nx = 1024, nz = 512: fft_postprocess_010's y stage (src/backend/cuda/poisson_fft.f90:822-924) works
  * column by column of (x mode, z mode), so the half axis may be z here too.  x3d_poisson_set_stretching_zfirst hands over

@@ -188,6 +188,11 @@ PROTOTYPES = {
     "x3d_poisson_zfirst_forward": (I, [VP, VP]),
     "x3d_poisson_zfirst_backward": (I, [VP, VP]),
     "x3d_poisson_solve_000_zfirst": (I, [VP, VP]),
+    "x3d_tds_solve_xfft_ok": (I, [VP, VP, c_int_p]),
+    "x3d_tds_solve_xfft": (I, [VP, VP, VP, VP]),
+    "x3d_poisson_xfft_ok": (I, [VP, c_int_p]),
+    "x3d_poisson_zfirst_middle_xpacked": (I, [VP]),
+    "x3d_c2c512_x_rows": (I, [VP, VP, ctypes.c_long, ctypes.c_long, I]),
     "x3d_tds_pair_zfirst": (I, [VP, VP, I, VP, VP, VP, VP, VP, VP, c_int_p]),
     "x3d_sfftz_create": (I, [VP, ctypes.POINTER(VP), c_int_p, I, I, I]),
     "x3d_sfftz_destroy": (I, [VP]),

@@ -769,6 +769,19 @@ class HipBackend:
                                                float(mean_target), ctypes.byref(out)))
         return out
 
+    def tds_apply_xfft_ok(self, tdsops):
+        """probe (nothing is launched): tds_apply_xfft takes this operator on this backend's x pencils"""
+        if self._decomposed(DIR_X):
+            return False
+        flag = ctypes.c_int(0)
+        _lib.check(self.lib.x3d_tds_solve_xfft_ok(self.h, tdsops.handle, ctypes.byref(flag)))
+        return bool(flag.value)
+
+    def tds_apply_xfft(self, du, u, tdsops):
+        """tds_apply along x whose result leaves transformed along x: every pencil's r as rfft(r), packed half-complex in
+        the pencil's 512 columns (csrc/xscan.hip k_xscan_tds_xfft); a missing kernel is an error (tds_apply_xfft_ok)"""
+        _lib.check(self.lib.x3d_tds_solve_xfft(self.h, du.ptr, u.ptr, tdsops.handle))
+
     def tds_apply(self, du, u, tdsops, direction, accumulate=False, scale=1.0):
         """tds_solve with an explicit direction; accumulate: du += scale * result"""
         if not self._decomposed(direction):

@@ -132,7 +132,7 @@ extern "C" int x3d_poisson_destroy(x3d_poisson *p)
     hipfftDestroy(p->plan_bw);
     if (p->fast512) { hipfftDestroy(p->plan_x_fw); hipfftDestroy(p->plan_x_bw); }
     if (p->y010 == 1) { hipfftDestroy(p->plan_x010_fw); hipfftDestroy(p->plan_x010_bw); }
-    hipFree(p->c); hipFree(p->waves); hipFree(p->ab); hipFree(p->work); hipFree(p->rwT); hipFree(p->rwZ);
+    hipFree(p->c); hipFree(p->waves); hipFree(p->ab); hipFree(p->work); hipFree(p->rwT); hipFree(p->rwZ); hipFree(p->rwZp);
     hipFree(p->lu[0]); hipFree(p->lu[1]); hipFree(p->luz[0]); hipFree(p->luz[1]);
     delete p;
     return 0;

@@ -1029,6 +1029,27 @@ extern "C" int x3d_tds_solve_acc(x3d_backend *b, real_t *du, const real_t *u, co
     return x3d_generic_tds_local(b, du, u, t, dir, accumulate, scale);
 }
 
+// x tds_solve whose result leaves transformed along x, packed half-complex (include/x3d2_hip.h; the kernel: csrc/xscan.hip)
+bool x3d_xscan_tds_xfft_ok(const x3d_backend *b, const x3d_tdsops *t);
+int x3d_xscan_tds_xfft(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t);
+extern "C" int x3d_tds_solve_xfft_ok(x3d_backend *b, const x3d_tdsops *t, int *ok)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(b && t && ok, "x3d_tds_solve_xfft_ok: null argument");
+    *ok = x3d_xscan_tds_xfft_ok(b, t) ? 1 : 0;
+    return 0;
+}
+extern "C" int x3d_tds_solve_xfft(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t)
+{
+    X3D_RANGE(__func__);
+    if (b) X3D_LAZY_SYNC(b);
+    X3D_LAZY_EAGER(b);
+    X3D_REQUIRE(b && du && u && t, "x3d_tds_solve_xfft: null argument");
+    X3D_REQUIRE(du != u, "x3d_tds_solve_xfft: du and u must be distinct blocks");
+    if (int rc = check_len(b, t, X3D_DIR_X, "tds_solve_xfft")) return rc;
+    return x3d_xscan_tds_xfft(b, du, u, t);
+}
+
 int x3d_ytile_tds_pair(x3d_backend *b, int dir, int mode, real_t *out1, real_t *out2, const real_t *in1, const real_t *in2,
                        const x3d_tdsops *ta, const x3d_tdsops *tb, const TileHalo *halo, int other0, int nother,
                        bool *done);  // xscan.hip

@@ -193,6 +193,68 @@ __global__ void __launch_bounds__(512) k_xscan_tds(real_t *__restrict__ du, cons
     }
 }
 
+// ---------------------------------------------------------------- tds_solve + forward x transform (round 7)
+// The first x operators of divergence_v2c next to the z-first 000 solve (csrc/zfirst.hip): everything between them and the
+// spectral division acts on each x column on its own with coefficients that do not depend on x, and the division's
+// multiplier is real and even in every wave number -- so the solve's forward x transform commutes with all of it and is
+// done here, on the pencil the wave already holds.  The solve is k_xscan_tds<8, false, 3>'s (same bits); its result
+// r[0 .. 511] leaves as F = rfft(r) (unnormalised, forward e^{-i}), 512 reals "packed half-complex":
+//   column 0 = Re F_0, column 1 = Re F_256, columns 2k, 2k + 1 = Re F_k, Im F_k (k = 1 .. 255); the pad columns stay.
+// A lane's 8 rows are 4 points z_m = r[2m] + i r[2m + 1], m = 4 lane + q: through the wave's own LDS region (FP256 real2_t,
+// no block barrier) to fft256_wave's layout, Z = FFT256(z), and the real-transform untangle
+//   F_k = (Z_k + conj Z_{256-k}) / 2 - (i / 2) W512^k (Z_k - conj Z_{256-k}),   F_256 = Re Z_0 - Im Z_0
+// with Z_{256-k} fetched through the region once more.  8 x FP256 + 256 twiddles = 40 KB of LDS would let four workgroups
+// share a CU; the 96 VGPRs the compiler takes allow two (bounded to 64 or 80 it spills: profiles/README.md).
+__global__ void __launch_bounds__(512, 4) k_xscan_tds_xfft(real_t *__restrict__ du, const real_t *__restrict__ u, int np,
+                                                           long pitch, CircOp co, const real2_t *__restrict__ twg)
+{
+    constexpr int Q = 8;
+    extern __shared__ real2_t xf[];  // [8][FP256] + 256 twiddles
+    real2_t *__restrict__ tws = xf + 8 * FP256;
+    if (threadIdx.x < 256) tws[threadIdx.x] = twg[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    real2_t *__restrict__ pen = xf + wave * FP256;
+    const int nwaves = gridDim.x * (blockDim.x >> 6);
+    const int p0 = blockIdx.x * (blockDim.x >> 6) + wave;
+    // slot of point m = 4 lane + q: q is mixed with bits 2, 3 of the lane, so that 16 neighbouring lanes' 16-byte
+    // writes go to 16 different bank groups (unmixed: four); the readers undo it
+    const int wsw = (lane >> 2) & 3, rsw = (lane >> 4) & 3;
+    real_t nb[Q];  // next pencil's rows, in flight while this one is solved
+    if (p0 < np) load_body<Q>(nb, u + (long)p0 * pitch, lane);
+    for (int p = p0; p < np; p += nwaves) {
+        real_t w[Q + 8], r[Q];
+        window_from_body<Q>(w, nb, lane);
+        if (p + nwaves < np) load_body<Q>(nb, u + (long)(p + nwaves) * pitch, lane);
+        circ_solve<Q, true>(w, r, co, lane);
+        wave_lds_fence();  // (the previous pencil's reads of the region come first)
+#pragma unroll
+        for (int q = 0; q < 4; q++) pen[4 * lane + (q ^ wsw)] = make_real2(r[2 * q], r[2 * q + 1]);
+        wave_lds_fence();
+        real2_t a[4], c[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) a[k] = pen[64 * k + ((lane & ~3) | ((lane & 3) ^ rsw))];
+        fft256_wave<-1>(a, pen, tws, lane);  // a[f] = Z[lane + 64 f]
+#pragma unroll
+        for (int f = 0; f < 4; f++) pen[lane + 64 * f] = a[f];
+        wave_lds_fence();
+#pragma unroll
+        for (int f = 0; f < 4; f++) c[f] = pen[(256 - lane - 64 * f) & 255];  // Z[256 - k], Z[256] = Z[0]
+        real2_t *__restrict__ o2 = reinterpret_cast<real2_t *>(du + (long)p * pitch);
+#pragma unroll
+        for (int f = 0; f < 4; f++) {
+            const int k = lane + 64 * f;
+            const real2_t wk = twiddle<-1>(tws, k);
+            const real_t er = 0.5 * (a[f].x + c[f].x), ei = 0.5 * (a[f].y - c[f].y);  // E_k = (Z_k + conj Z_{256-k}) / 2
+            const real_t dr = 0.5 * (a[f].y + c[f].y), di = 0.5 * (c[f].x - a[f].x);  // O_k = -(i / 2) (Z_k - conj Z_{256-k})
+            real2_t F = make_real2(er + (wk.x * dr - wk.y * di), ei + (wk.x * di + wk.y * dr));
+            if (f == 0 && lane == 0) F = make_real2(a[0].x + a[0].y, a[0].x - a[0].y);  // (F_0, F_256)
+            o2[k] = F;  // 16 bytes per lane, 1 KB contiguous per instruction
+        }
+    }
+}
+
 // ---------------------------------------------------------------- tds_solve of a field that is still to be formed
 // The first x operators of the pressure correction act on the velocity the RK / AB stage has just produced
 // (y = base + sum c_k x_k, src/time_integrator.f90:166-282 -> divergence_v2c, src/vector_calculus.f90:160-175).
@@ -1552,6 +1614,31 @@ int x3d_xscan_tds(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops 
 #undef LAUNCH
     X3D_HIP(hipGetLastError());
     *done = true;
+    return 0;
+}
+
+// tds_solve + packed forward x transform (k_xscan_tds_xfft): 512-row pencils of an operator in the circulant form
+int x3d_fft512_init();                   // fft512.hip
+const real2_t *x3d_fft512_twiddles();
+bool x3d_xscan_tds_xfft_ok(const x3d_backend *b, const x3d_tdsops *t)
+{
+    // (FP64 only: the FP32 flavour builds the kernel but has not been held to its yardsticks in this form)
+    return sizeof(real_t) == 8 && b->sw.x_fast && !b->sw.no_xfft_div && b->nx == 512 && b->nxp % 2 == 0 && xscan_ok(t) && t->tab.Q == 8 &&
+           t->tab.bulk_only && t->n_tds == 512 && t->tab.n_rhs == 512 && stencil_narrow(t) && t->uniform && t->circ_ok &&
+           !b->sw.no_circ;
+}
+int x3d_xscan_tds_xfft(x3d_backend *b, real_t *du, const real_t *u, const x3d_tdsops *t)
+{
+    X3D_REQUIRE(x3d_xscan_tds_xfft_ok(b, t), "x3d_tds_solve_xfft: not on offer for this operator (x3d_tds_solve_xfft_ok)");
+    if (int rc = x3d_fft512_init()) return rc;
+    const int np = b->ny * b->nz;
+    const size_t lds = sizeof(real2_t) * (8 * FP256 + 256);
+    int blocks = (np + 7) / 8;
+    blocks = blocks > 1024 ? 1024 : blocks;  // (the plain circulant form's cap; two workgroups per CU are resident at a time)
+    ProfScope ps(b, X3D_K_TDS_FWD, X3D_DIR_X);
+    hipLaunchKernelGGL(k_xscan_tds_xfft, dim3(blocks), dim3(512), lds, b->stream, du, u, np, (long)b->nxp, t->circ,
+                       x3d_fft512_twiddles());
+    X3D_HIP(hipGetLastError());
     return 0;
 }
 

@@ -16,6 +16,9 @@
 // numbers; it lives in the solver's spectral workspace.  The spectral operation is the reference's sequence of
 // rotations, division and inverse rotations with the x index mirrored above nx / 2 the way y and z are there (the
 // rotations cancel pairwise: |b - i a| = 1, so any consistent choice gives the result up to rounding).
+// Round 7: where the divergence's x operators have transformed along x already (k_xscan_tds_xfft, csrc/xscan.hip: rows
+// packed half-complex) the forward x pass is not run, the y pass takes the reciprocal wave numbers of the packed columns and
+// the inverse x pass untangles first (x3d_poisson_zfirst_middle_xpacked): 4.5 passes.
 #include <vector>
 
 #include "fft_util.h"
@@ -27,14 +30,17 @@
 int x3d_ztile_fft_run(x3d_backend *b, real_t *f, const ZfArg &zf, bool fwd, int y0, int nyr);
 
 // rwZ[kz][x][y] = -1 / waves(min(x, nx - x), y, kz)  (0 where waves < 1e-16); waves = [nz][ny][nxs] (x: nx/2+1 modes)
+// packed: column x of a spectrum whose x axis is packed half-complex (k_xscan_tds_xfft, csrc/xscan.hip) carries the x
+// mode 0, nx / 2 for x = 0, 1 and x >> 1 otherwise
 __global__ void __launch_bounds__(256)
-    k_zh_rw(real_t *__restrict__ rwZ, const real_t *__restrict__ waves, int nx, int ny, int nxs)
+    k_zh_rw(real_t *__restrict__ rwZ, const real_t *__restrict__ waves, int nx, int ny, int nxs, int packed)
 {
     __shared__ real_t t[32][33];
     const int kz = blockIdx.z, x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int r = ty; r < 32; r += 8) {
-        const int x = x0 + tx, y = y0 + r, xm = x <= nx / 2 ? x : nx - x;
+        const int x = x0 + tx, y = y0 + r;
+        const int xm = packed ? (x < 2 ? x * (nx / 2) : x >> 1) : (x <= nx / 2 ? x : nx - x);
         const real_t wv = waves[((size_t)kz * ny + y) * nxs + xm];
         t[r][tx] = wv < 1.e-16 ? 0.0 : -1.0 / wv;
     }
@@ -43,10 +49,16 @@ __global__ void __launch_bounds__(256)
 }
 
 // complex transform of contiguous rows of 512 (the x axis of C), one row per wave, in place
-template <int S>
+// UNT (S = +1): the row arrives packed half-complex along x (k_xscan_tds_xfft, csrc/xscan.hip: columns 2m, 2m + 1 hold the
+// z / y-spectral values A_m, B_m of Re F_m, Im F_m; columns 0, 1 those of F_0, F_256) and is untangled in registers first:
+//   H_m = A_m + i B_m,  H_{512-m} = A_m - i B_m  (m = 1 .. 255),  H_0 = column 0,  H_256 = column 1
+// A lane loads 32 contiguous bytes (columns 2m, 2m + 1, m = l + 64 j): H_m is its own point j, the partner H_{512-m} goes
+// to its owner through the wave's LDS region.
+template <int S, bool UNT = false>
 __global__ void __launch_bounds__(512)
     k_c2c512_x(real2_t *__restrict__ c, const real2_t *__restrict__ twg, long nrows, long pitch)
 {
+    static_assert(!UNT || S > 0, "the untangle belongs to the inverse transform");
     extern __shared__ real2_t zx[];  // [8][FP] + 256 twiddles
     real2_t *__restrict__ tws = zx + 8 * FP;
     if (threadIdx.x < 256) tws[threadIdx.x] = twg[threadIdx.x];
@@ -56,16 +68,32 @@ __global__ void __launch_bounds__(512)
     long row = (long)blockIdx.x * 8 + w;
     const long step = (long)gridDim.x * 8;
     real2_t a[8], nx8[8];
+    // (UNT: nx8[2 j], nx8[2 j + 1] = columns 2 m, 2 m + 1 of m = l + 64 j)
+    auto col = [&](int k) { return UNT ? 2 * (l + 64 * (k >> 1)) + (k & 1) : l + 64 * k; };
     if (row < nrows) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) nx8[k] = c[row * pitch + l + 64 * k];
+        for (int k = 0; k < 8; k++) nx8[k] = c[row * pitch + col(k)];
     }
     for (; row < nrows; row += step) {
+        if (UNT) {
+            wave_lds_fence();  // (the previous row's reads of the region come first)
 #pragma unroll
-        for (int k = 0; k < 8; k++) a[k] = nx8[k];
+            for (int j = 0; j < 4; j++) {
+                const real2_t A = nx8[2 * j], B = nx8[2 * j + 1];
+                const int m = l + 64 * j;
+                a[j] = m ? make_real2(A.x - B.y, A.y + B.x) : A;
+                pen[m ? 512 - m : 256] = m ? make_real2(A.x + B.y, A.y - B.x) : B;  // slots 511 .. 257 ; m = 0: H_256
+            }
+            wave_lds_fence();
+#pragma unroll
+            for (int k = 4; k < 8; k++) a[k] = pen[l + 64 * k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) a[k] = nx8[k];
+        }
         if (row + step < nrows) {
 #pragma unroll
-            for (int k = 0; k < 8; k++) nx8[k] = c[(row + step) * pitch + l + 64 * k];
+            for (int k = 0; k < 8; k++) nx8[k] = c[(row + step) * pitch + col(k)];
         }
         fft512_wave<S>(a, pen, tws, l);
 #pragma unroll
@@ -198,7 +226,7 @@ static bool zfirst010_sizes(const x3d_poisson *p)
            b->nx == 1024 && b->nz == 512 && b->ny >= 256 && p->c_elems >= (size_t)257 * 256 * ZH010_PX;
 }
 
-// the z-first solve is on offer for this solver (X3D_NO_ZFIRST=1: never); builds the reciprocal wave numbers on first use
+// the z-first solve is on offer for this solver (X3D_NO_ZFIRST=1: never); the reciprocal wave numbers: zh_table
 int x3d_zfirst_arg(x3d_poisson *p, ZfArg *out, bool *ok)
 {
     *ok = false;
@@ -217,13 +245,24 @@ int x3d_zfirst_arg(x3d_poisson *p, ZfArg *out, bool *ok)
         return 0;
     }
     if (!zfirst_sizes(p)) return 0;
-    if (!p->rwZ) {
-        X3D_HIP(hipMalloc(&p->rwZ, sizeof(real_t) * 257 * 512 * 512));
-        hipLaunchKernelGGL(k_zh_rw, dim3(16, 16, 257), dim3(256), 0, p->b->stream, p->rwZ, p->waves, p->nx, p->ny, p->nxs);
-        X3D_HIP(hipGetLastError());
-    }
+    if (int rc = x3d_fft512_init()) return rc;
     if (out) *out = ZfArg{p->c, x3d_fft512_twiddles(), p->ny, (long)ZH_PX};
     *ok = true;
+    return 0;
+}
+
+// the reciprocal wave numbers of the y middle, built on first use: for the spectrum in natural x order (p->rwZ) or for the
+// one whose x axis arrives packed half-complex (p->rwZp); a solver that only ever runs one form holds one table
+static int zh_table(x3d_poisson *p, bool packed, const real_t **out)
+{
+    real_t *&tab = packed ? p->rwZp : p->rwZ;
+    if (!tab) {
+        X3D_HIP(hipMalloc(&tab, sizeof(real_t) * 257 * 512 * 512));
+        hipLaunchKernelGGL(k_zh_rw, dim3(16, 16, 257), dim3(256), 0, p->b->stream, tab, p->waves, p->nx, p->ny, p->nxs,
+                           packed ? 1 : 0);
+        X3D_HIP(hipGetLastError());
+    }
+    *out = tab;
     return 0;
 }
 
@@ -243,19 +282,37 @@ extern "C" int x3d_poisson_zfirst_ok(x3d_poisson *p, int *ok)
     return 0;
 }
 
-template <int S>
-static int c2c_x(x3d_poisson *p, int kz0, int nkz)
+template <int S, bool UNT = false>
+static int c2c_x_rows(x3d_backend *b, real2_t *c, long nrows, long pitch)
 {
     const int lds = sizeof(real2_t) * (8 * FP + 256);
-    X3D_LDS_OPTIN(p->b, (k_c2c512_x<S>));
-    const long nrows = (long)nkz * p->ny;
+    X3D_LDS_OPTIN(b, (k_c2c512_x<S, UNT>));
     long blocks = (nrows + 7) / 8;
     if (blocks > 2048) blocks = 2048;
-    ProfScope ps(p->b, X3D_K_FFT, S < 0 ? 1 : 2);
-    hipLaunchKernelGGL((k_c2c512_x<S>), dim3((unsigned)blocks), dim3(512), lds, p->b->stream,
-                       p->c + (long)kz0 * p->ny * ZH_PX, x3d_fft512_twiddles(), nrows, (long)ZH_PX);
+    ProfScope ps(b, X3D_K_FFT, S < 0 ? 1 : 2);
+    hipLaunchKernelGGL((k_c2c512_x<S, UNT>), dim3((unsigned)blocks), dim3(512), lds, b->stream, c, x3d_fft512_twiddles(), nrows,
+                       pitch);
     X3D_HIP(hipGetLastError());
     return 0;
+}
+template <int S, bool UNT = false>
+static int c2c_x(x3d_poisson *p, int kz0, int nkz)
+{
+    return c2c_x_rows<S, UNT>(p->b, p->c + (long)kz0 * p->ny * ZH_PX, (long)nkz * p->ny, (long)ZH_PX);
+}
+
+// the x passes of the z-first solve on rows of the caller's (tests, tools): nrows rows of 512 complex numbers, `pitch`
+// complex numbers apart, in place.  mode -1: forward, +1: inverse, +2: inverse of rows packed half-complex along x
+extern "C" int x3d_c2c512_x_rows(x3d_backend *b, x3d_real *c, long nrows, long pitch, int mode)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(b && c && nrows > 0 && pitch >= 512, "x3d_c2c512_x_rows: bad argument");
+    X3D_REQUIRE(mode == -1 || mode == 1 || mode == 2, "x3d_c2c512_x_rows: mode %d", mode);
+    X3D_LAZY_SYNC(b);
+    if (int rc = x3d_fft512_init()) return rc;
+    real2_t *c2 = reinterpret_cast<real2_t *>(c);
+    if (mode == -1) return c2c_x_rows<-1>(b, c2, nrows, pitch);
+    return mode == 1 ? c2c_x_rows<1>(b, c2, nrows, pitch) : c2c_x_rows<1, true>(b, c2, nrows, pitch);
 }
 
 // C (z already transformed) -> x forward ; y forward + process_spectral_000 + y inverse ; x inverse -> C
@@ -299,9 +356,40 @@ extern "C" int x3d_poisson_zfirst_middle(x3d_poisson *p)
     }
     // (the three kernels on groups of 8 .. 64 kz planes, so that a group stays in the memory-side cache between them:
     // measured, no gain -- profiles/README.md)
+    const real_t *rw;
+    if (int rc = zh_table(p, false, &rw)) return rc;
     if (int rc = c2c_x<-1>(p, 0, 257)) return rc;
-    if (int rc = x3d_fft512_run_zh(p->b, p->c, ZH_PX, 0, 257, p->rwZ, p->ab, p->nx, p->ny, p->nz)) return rc;
+    if (int rc = x3d_fft512_run_zh(p->b, p->c, ZH_PX, 0, 257, rw, p->ab, p->nx, p->ny, p->nz)) return rc;
     return c2c_x<1>(p, 0, 257);
+}
+
+// ---- the middle for a spectrum whose x axis is transformed already, packed half-complex (the divergence's x operators did
+// it: x3d_tds_solve_xfft, csrc/xscan.hip).  The y middle is linear over the complex numbers column by column and its
+// multiplier is real: it runs unchanged with the reciprocal wave numbers of the columns' x modes (zh_table); the inverse x
+// pass untangles in registers first.  4.5 passes over the spectrum instead of 6.5.  X3D_NO_XFFT_DIV=1: not on offer
+extern "C" int x3d_poisson_xfft_ok(x3d_poisson *p, int *ok)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(p && ok, "x3d_poisson_xfft_ok: null argument");
+    *ok = 0;
+    if (p->ext_middle || p->stretched || p->b->sw.no_xfft_div) return 0;
+    bool o = false;
+    if (int rc = x3d_zfirst_arg(p, nullptr, &o)) return rc;
+    *ok = o ? 1 : 0;
+    return 0;
+}
+extern "C" int x3d_poisson_zfirst_middle_xpacked(x3d_poisson *p)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(p, "x3d_poisson_zfirst_middle_xpacked: null argument");
+    int ok = 0;
+    if (int rc = x3d_poisson_xfft_ok(p, &ok)) return rc;
+    X3D_REQUIRE(ok, "x3d_poisson_zfirst_middle_xpacked: not on offer for this solver (x3d_poisson_xfft_ok)");
+    X3D_LAZY_EAGER(p->b);
+    const real_t *rw;
+    if (int rc = zh_table(p, true, &rw)) return rc;
+    if (int rc = x3d_fft512_run_zh(p->b, p->c, ZH_PX, 0, 257, rw, p->ab, p->nx, p->ny, p->nz)) return rc;
+    return c2c_x<1, true>(p, 0, 257);
 }
 
 // ---- proxy of a z-first solve whose middle the CALLER runs (include/x3d2_hip.h, x3d_poisson_create_proxy)

@@ -381,6 +381,19 @@ class HipPoissonFFT:
     def zfirst_middle(self):
         _lib.check(self.backend.lib.x3d_poisson_zfirst_middle(self.h))
 
+    def xfft_ok(self):
+        """the z-first 000 solve also takes a spectrum whose x axis is transformed already, packed half-complex, by the
+        x operators of the divergence (HipBackend.tds_apply_xfft): zfirst_middle_xpacked() then skips the forward x pass
+        (csrc/zfirst.hip; X3D_NO_XFFT_DIV=1: never)"""
+        if not self.zfirst_ok() or self.case != "000":
+            return False
+        ok = ctypes.c_int(0)
+        _lib.check(self.backend.lib.x3d_poisson_xfft_ok(self.h, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def zfirst_middle_xpacked(self):
+        _lib.check(self.backend.lib.x3d_poisson_zfirst_middle_xpacked(self.h))
+
     def zfirst_forward(self, f):
         _lib.check(self.backend.lib.x3d_poisson_zfirst_forward(self.h, f.ptr))
 

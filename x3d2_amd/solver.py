@@ -122,6 +122,14 @@ class Solver:
             z = self.zdirps
             self._zfirst = (backend.zfirst_pairs_ok(z.interpl_v2p, z.stagder_v2p)
                             and backend.zfirst_pairs_ok(z.interpl_p2v, z.stagder_p2v))
+        # ... and the solve's forward x transform rides on the divergence's three x operators (csrc/xscan.hip
+        # k_xscan_tds_xfft; X3D_NO_XFFT_DIV=1: a pass of its own): asked once, here, for the solver and both operators
+        x = self.xdirps
+        self._xfft_div = bool(self._zfirst and getattr(pf, "xfft_ok", lambda: False)()
+                              and not hasattr(pf, "zfirst_solve_pipelined") and backend.comm.size == 1
+                              and not any(backend._decomposed(d) for d in (DIR_X, DIR_Y, DIR_Z))
+                              and backend.tds_apply_xfft_ok(x.stagder_v2p) and backend.tds_apply_xfft_ok(x.interpl_v2p))
+        self.n_xfft_div = 0                              # pressure corrections that took that form (tests)
         self.shift_request = None  # device scalar to add to u before transeq_x uses it (field_mean_shift)
         self.pending_walls = None  # wall fields to stamp on u, v, w inside the divergence's first kernels
         # (round 6) the case's next define_BC wants field_mean_shift(u, mean_request): taken along by the kernel that
@@ -404,8 +412,20 @@ class Solver:
         # a snapshot wants this correction's pressure: on the z-first 000 and the row-interleaved 010 path it never exists
         # as a field, so this one correction takes the plain z pair -> solve_poisson -> z pair and p is copied out
         want_p = self.keep_pressure and self.pressure_wanted
+        # z-first 000 solve, no walls, no mean request: the three x operators also do the solve's forward x transform; t1,
+        # t2, t3 and everything up to the spectrum are then packed half-complex along x.  A pending RK / AB update is
+        # formed by a lincomb of its own first (the bits of the operator's prologue, one more read of the new velocity):
+        # every way of forming the velocity must lead to the same form of the solve, the stage-in-z-launch test
+        # (X3D_NO_EPI3=1 against the default) asks for equal bits
+        xfft = self._xfft_div and not want_p and mean is None and all(wl is None for wl in walls)
         for out, fld, op, wall in ((t1, u, x.stagder_v2p, walls[0]), (t2, v, x.interpl_v2p, walls[1]),
                                    (t3, w, x.interpl_v2p, walls[2])):
+            if xfft:
+                spec = upd.pop(fld.data.data_ptr(), None)
+                if spec is not None:
+                    b.lincomb(*spec)
+                b.tds_apply_xfft(out, fld if spec is None else spec[0], op)
+                continue
             spec = upd.pop(fld.data.data_ptr(), None)
             take_mean = fld is u and mean is not None and defer_grad and b.comm.size == 1 and not b._decomposed(DIR_X)
             if spec is None:
@@ -452,7 +472,7 @@ class Solver:
             b.tds_apply(a2, t3, y.interpl_v2p, DIR_Y)
             # 000 solve at 512^3: z-first -- the z pairs on either side transform along z on their tiles, the divergence
             # and the pressure never exist as fields (csrc/zfirst.hip)
-            if self._zfirst and not want_p and self._zfirst_solve(a1, a2, t2, t3):
+            if self._zfirst and not want_p and self._zfirst_solve(a1, a2, t2, t3, xpacked=xfft):
                 b.tds_pair(1, a1, a2, t2, None, y.interpl_p2v, y.stagder_p2v, DIR_Y)   # p_sx, dpdy_sx
                 b.tds_apply(t1, t3, y.interpl_p2v, DIR_Y)                              # dpdz_sx
                 return self._finish_pressure_correction(u, v, w, (t1, t2, t3, a1, a2), defer_grad)
@@ -500,10 +520,20 @@ class Solver:
                 b.tds_apply(t1, t3, y.interpl_p2v, DIR_Y)
         self._finish_pressure_correction(u, v, w, (t1, t2, t3, a1, a2), defer_grad)
 
-    def _zfirst_solve(self, a1, a2, t2, t3):
+    def _zfirst_solve(self, a1, a2, t2, t3, xpacked=False):
         """div = interpl_z(a1) + stagder_z(a2) ; p = poisson(div) ; t2 = interpl_z(p), t3 = stagder_z(p) with the z
-        transforms of the 000 solve on the tiles of the two z pairs; False: not served for these operators, nothing done"""
+        transforms of the 000 solve on the tiles of the two z pairs; False: not served for these operators, nothing done.
+        xpacked: a1, a2 are transformed along x already, packed half-complex (HipBackend.tds_apply_xfft)"""
         b, z = self.backend, self.zdirps
+        if xpacked:
+            if not b.tds_pair_zfirst(0, None, None, a1, a2, z.interpl_v2p, z.stagder_v2p):
+                raise X3dError("pressure_correction: x-transformed operands, but the z-first pair declined the divergence")
+            b.poisson_fft.zfirst_middle_xpacked()
+            if not b.tds_pair_zfirst(1, t2, t3, None, None, z.interpl_p2v, z.stagder_p2v):
+                raise X3dError("pressure_correction: the z-first pair served the divergence but not the gradient")
+            self.n_zfirst += 1
+            self.n_xfft_div += 1
+            return True
         pipe = getattr(b.poisson_fft, "zfirst_solve_pipelined", None)
         if pipe is not None and not b._decomposed(DIR_Z) and \
                 pipe(a1, a2, t2, t3, z.interpl_v2p, z.stagder_v2p, z.interpl_p2v, z.stagder_p2v):
