@@ -568,6 +568,34 @@ int x3d_tds_solve_xfft(x3d_backend *b, x3d_real *du, const x3d_real *u, const x3
 int x3d_poisson_xfft_ok(x3d_poisson *p, int *ok);
 int x3d_poisson_zfirst_middle_xpacked(x3d_poisson *p);
 int x3d_c2c512_x_rows(x3d_backend *b, x3d_real *c, long nrows, long pitch, int mode);
+/* ... and its inverse x transform inside the last three x operators of gradient_c2v (src/vector_calculus.f90:318-330, with
+ * the velocity update of src/solver.f90:731-733 folded in).  Between the division and those operators run the y inverse of
+ * the middle, the z pair with its complex-to-real z transform, the y pair and the single y operator: x-independent and
+ * real-linear column by column, so the packed columns A_k, B_k leave the z transform as Re G_k(z), Im G_k(z) and the three
+ * gradient fields arrive at the x operators as pack(rfft_x(field)).  The operators invert the transform on the pencil the
+ * wave holds (unnormalised: 512 x the rows, the scaling of the solve's inverse x pass): 2.5 passes over the spectrum, no x
+ * pass in either direction.  FP64, 512-row pencils, operators in the circulant form, one rank; X3D_NO_XFFT_GRAD=1 (and
+ * X3D_NO_XFFT_DIV=1): not on offer.
+ *   x3d_tds_solve_ixfft_ok            *ok = 1: this operator's pencils are ones the kernel takes
+ *   x3d_tds_solve_ixfft               u += scale * tds_solve(g') along x, g' = 512 x the field whose pencils g holds packed
+ *                                     (tds_solve of src/solver.f90:731-733's operands; x3d_tds_solve_acc's arithmetic)
+ *   x3d_transeq_x_update_xinv_ok      *ok = 1: x3d_transeq_x_update_xinv takes these two operators
+ *   x3d_transeq_x_update_xinv         x3d_transeq_x_update (transeq_x of src/solver.f90:320-377 on a velocity whose
+ *                                     correction is pending) for gu, gv, gw that are still packed; *done = 0: not served,
+ *                                     nothing was done.  Bit-identical to x3d_tds_solve_ixfft x 3 + x3d_transeq along x
+ *   x3d_poisson_xfft_grad_ok          *ok = 1: x3d_poisson_xfft_ok and the switch is not set
+ *   x3d_poisson_zfirst_middle_xpacked2  the middle for a spectrum packed along x that STAYS packed: the y pass (forward,
+ *                                     division -- process_spectral_000, src/backend/omp/kernels/spectral_processing.f90:
+ *                                     7-106 -- inverse) and nothing else */
+int x3d_tds_solve_ixfft_ok(x3d_backend *b, const x3d_tdsops *t, int *ok);
+int x3d_tds_solve_ixfft(x3d_backend *b, x3d_real *u, const x3d_real *g, const x3d_tdsops *t, x3d_real scale);
+int x3d_transeq_x_update_xinv_ok(x3d_backend *b, const x3d_tdsops *op_u, const x3d_tdsops *op_vw, int *ok);
+int x3d_transeq_x_update_xinv(x3d_backend *b, x3d_real *du, x3d_real *dv, x3d_real *dw, x3d_real *u, x3d_real *v, x3d_real *w,
+                              x3d_real nu, const x3d_tdsops *der1st, const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd,
+                              const x3d_tdsops *der2nd_sym, const x3d_real *gu, const x3d_real *gv, const x3d_real *gw,
+                              const x3d_tdsops *op_u, const x3d_tdsops *op_vw, x3d_real scale, int *done);
+int x3d_poisson_xfft_grad_ok(x3d_poisson *p, int *ok);
+int x3d_poisson_zfirst_middle_xpacked2(x3d_poisson *p);
 /* round 6: the same reordering for the channel's solve -- poisson_010 (src/poisson_fft.f90:228-242) on a stretched y with
  * 256 cell rows, nx = 1024, nz = 512: fft_postprocess_010's y stage (src/backend/cuda/poisson_fft.f90:822-924) works
  * column by column of (x mode, z mode), so the half axis may be z here too.  x3d_poisson_set_stretching_zfirst hands over

@@ -193,6 +193,12 @@ PROTOTYPES = {
     "x3d_poisson_xfft_ok": (I, [VP, c_int_p]),
     "x3d_poisson_zfirst_middle_xpacked": (I, [VP]),
     "x3d_c2c512_x_rows": (I, [VP, VP, ctypes.c_long, ctypes.c_long, I]),
+    "x3d_tds_solve_ixfft_ok": (I, [VP, VP, c_int_p]),
+    "x3d_tds_solve_ixfft": (I, [VP, VP, VP, VP, D]),
+    "x3d_transeq_x_update_xinv_ok": (I, [VP, VP, VP, c_int_p]),
+    "x3d_transeq_x_update_xinv": (I, [VP, VP, VP, VP, VP, VP, VP, D, VP, VP, VP, VP, VP, VP, VP, VP, VP, D, c_int_p]),
+    "x3d_poisson_xfft_grad_ok": (I, [VP, c_int_p]),
+    "x3d_poisson_zfirst_middle_xpacked2": (I, [VP]),
     "x3d_tds_pair_zfirst": (I, [VP, VP, I, VP, VP, VP, VP, VP, VP, c_int_p]),
     "x3d_sfftz_create": (I, [VP, ctypes.POINTER(VP), c_int_p, I, I, I]),
     "x3d_sfftz_destroy": (I, [VP]),

@@ -574,6 +574,27 @@ class HipBackend:
                                                  op_u.handle, op_vw.handle, float(scale), ctypes.byref(flag)))
         return bool(flag.value)
 
+    def transeq_x_update_xinv_ok(self, op_u, op_vw):
+        """probe (nothing is launched): transeq_x_update_xinv takes these two operators on this backend's x pencils"""
+        if self._decomposed(DIR_X):
+            return False
+        flag = ctypes.c_int(0)
+        _lib.check(self.lib.x3d_transeq_x_update_xinv_ok(self.h, op_u.handle, op_vw.handle, ctypes.byref(flag)))
+        return bool(flag.value)
+
+    def transeq_x_update_xinv(self, du, dv, dw, u, v, w, nu, dirps, grads, op_u, op_vw, scale):
+        """transeq_x_update for grads that are still transformed along x, packed half-complex (the z-first solve without
+        its inverse x pass): the kernel inverts each pencil first (csrc/xscan.hip, k_xscan_transeq2x3<XINV>); False: not
+        served, nothing was done"""
+        if self._decomposed(DIR_X):
+            return False
+        flag = ctypes.c_int(0)
+        _lib.check(self.lib.x3d_transeq_x_update_xinv(self.h, du.ptr, dv.ptr, dw.ptr, u.ptr, v.ptr, w.ptr, float(nu),
+                                                      dirps.der1st.handle, dirps.der1st_sym.handle, dirps.der2nd.handle,
+                                                      dirps.der2nd_sym.handle, grads[0].ptr, grads[1].ptr, grads[2].ptr,
+                                                      op_u.handle, op_vw.handle, float(scale), ctypes.byref(flag)))
+        return bool(flag.value)
+
     def transeq_x_update_rot(self, du, dv, dw, u, v, w, nu, dirps, grads, op_u, op_vw, scale, omega, u_shift=None):
         """transeq_x_update and transeq_x_rot in one launch (csrc/xwide.hip, k_xwide_transeq3_upd): pending correction,
         bulk-velocity shift, transeq_x, rotation forcing; False: not served, nothing was done"""
@@ -781,6 +802,20 @@ class HipBackend:
         """tds_apply along x whose result leaves transformed along x: every pencil's r as rfft(r), packed half-complex in
         the pencil's 512 columns (csrc/xscan.hip k_xscan_tds_xfft); a missing kernel is an error (tds_apply_xfft_ok)"""
         _lib.check(self.lib.x3d_tds_solve_xfft(self.h, du.ptr, u.ptr, tdsops.handle))
+
+    def tds_apply_ixfft_ok(self, tdsops):
+        """probe (nothing is launched): tds_apply_ixfft takes this operator on this backend's x pencils"""
+        if self._decomposed(DIR_X):
+            return False
+        flag = ctypes.c_int(0)
+        _lib.check(self.lib.x3d_tds_solve_ixfft_ok(self.h, tdsops.handle, ctypes.byref(flag)))
+        return bool(flag.value)
+
+    def tds_apply_ixfft(self, du, g, tdsops, scale):
+        """du += scale * tds_apply along x of the field whose pencils g holds as rfft, packed half-complex in the pencil's
+        512 columns -- unnormalised: 512 x the field (csrc/xscan.hip k_xscan_tds_ixfft); a missing kernel is an error
+        (tds_apply_ixfft_ok)"""
+        _lib.check(self.lib.x3d_tds_solve_ixfft(self.h, du.ptr, g.ptr, tdsops.handle, float(scale)))
 
     def tds_apply(self, du, u, tdsops, direction, accumulate=False, scale=1.0):
         """tds_solve with an explicit direction; accumulate: du += scale * result"""

@@ -140,7 +140,7 @@ struct PencilGeom {
 struct x3d_switches {
     long no_via_x, no_xscan, no_ygen, no_ytile, no_q5, no_direct, sfft010_split_xy;
     long no_circ, no_halo_circ, no_uniform, xscan_p1, no_ztile, no_tds_pair, no_npw2, no_tile3, xdir_generic, no_xcirc;
-    long no_tds_lincomb, no_zfirst010, no_zfirst, no_xwide, no_xwide_upd, no_xfft_div;
+    long no_tds_lincomb, no_zfirst010, no_zfirst, no_xwide, no_xwide_upd, no_xfft_div, no_xfft_grad;
     long no_spectral_pad, no_fft512, no_rwt, no_r2c512, no_y010, y010_no_db, no_onchip2, no_slab_fused_z;
     long lazy_dump, lazy_report, lazy_keep_zero_terms;
     long pad_x;         // doubles of row padding; X3D_SW_UNSET: the backend's own rule (backend.hip)

@@ -160,3 +160,50 @@ __device__ __forceinline__ void fft256_wave(real2_t (&a)[4], real2_t *__restrict
     }
     wave_lds_fence();
 }
+
+// ---- inverse of the packed real transform of one 512-row pencil per wave (the x operators that take a gradient still
+// transformed along x: k_xscan_tds_ixfft and k_xscan_transeq2x3<XINV>, csrc/xscan.hip).  in: g[f] = columns 2k, 2k + 1 of
+// the pencil at k = l + 64 f, packed half-complex as k_xscan_tds_xfft stores it: (Re F_k, Im F_k), k = 0: (Re F_0,
+// Re F_256).  out: r[q] = 512 x row 8 l + q of the real pencil whose rfft is F -- unnormalised like k_c2c512_x<+1>.
+//   Z_k = (F_k + conj F_{256-k}) + i W512^{-k} (F_k - conj F_{256-k}),  Z_0 = (F_0 + F_256) + i (F_0 - F_256)
+//   512 (r[2m] + i r[2m + 1]) = FFT256<+1>(Z)_m
+// The partner F_{256-k} and the hand-over from fft256_wave's layout (m = l + 64 f) to the lane's own rows (m = 4 l + q)
+// go through the wave's own region pen (FP256 real2_t), no block barrier; the slots of the hand-over are mixed as in the
+// forward kernel, mirrored.  Every product pair is spelled out (fma_r): the two kernels must give the same bits.
+__device__ __forceinline__ void load_packed(real2_t (&g)[4], const real_t *__restrict__ row, int l)
+{
+    const real2_t *__restrict__ g2 = reinterpret_cast<const real2_t *>(row);
+#pragma unroll
+    for (int f = 0; f < 4; f++) g[f] = g2[l + 64 * f];  // 16 bytes per lane, 1 KB contiguous per instruction
+}
+__device__ __forceinline__ void irfft512_packed_wave(const real2_t (&g)[4], real_t (&r)[8], real2_t *__restrict__ pen,
+                                                     const real2_t *__restrict__ tw, int l)
+{
+    real2_t a[4];
+    wave_lds_fence();  // (the caller's reads of this region come first)
+#pragma unroll
+    for (int f = 0; f < 4; f++) pen[l + 64 * f] = g[f];
+    wave_lds_fence();
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+        const int k = l + 64 * f;
+        const real2_t c = pen[(256 - k) & 255];  // F_{256-k}  (k = 0: not used)
+        const real2_t wk = twiddle<1>(tw, k);    // W512^{-k}
+        const real_t sx = g[f].x + c.x, sy = g[f].y - c.y;  // F_k + conj F_{256-k}
+        const real_t dx = g[f].x - c.x, dy = g[f].y + c.y;  // F_k - conj F_{256-k}
+        // + i wk d = (-(wk.x dy + wk.y dx), wk.x dx - wk.y dy)
+        a[f] = make_real2(sx - fma_r(wk.x, dy, wk.y * dx), sy + fma_r(wk.x, dx, -(wk.y * dy)));
+        if (f == 0) a[f] = l == 0 ? make_real2(g[0].x + g[0].y, g[0].x - g[0].y) : a[f];
+    }
+    fft256_wave<1>(a, pen, tw, l);  // a[f] = 512 (r[2m] + i r[2m + 1]), m = l + 64 f
+    const int wsw = (l >> 2) & 3, rsw = (l >> 4) & 3;
+#pragma unroll
+    for (int f = 0; f < 4; f++) pen[64 * f + ((l & ~3) | ((l & 3) ^ rsw))] = a[f];
+    wave_lds_fence();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const real2_t v = pen[4 * l + (q ^ wsw)];
+        r[2 * q] = v.x;
+        r[2 * q + 1] = v.y;
+    }
+}

@@ -46,6 +46,7 @@ static const SwEntry g_table[] = {
     F("X3D_NO_R2C512", no_r2c512),                // Poisson with 512-point x rows: rocFFT's real-to-complex x pass
     F("X3D_NO_ZFIRST", no_zfirst),                // Poisson: no z-first solve on offer
     F("X3D_NO_XFFT_DIV", no_xfft_div),            // z-first 000 solve: its forward x transform as a pass of its own, not in the divergence's x operators
+    F("X3D_NO_XFFT_GRAD", no_xfft_grad),          // z-first 000 solve: its inverse x transform as a pass of its own, not in the gradient's x operators
     F("X3D_NO_ZFIRST010", no_zfirst010),          // the channel's 010 solve: its x-first form
     F("X3D_NO_Y010", no_y010),                    // Poisson 010: the 3-D transforms with post-processing kernels between them
     F("X3D_Y010_NO_DB", y010_no_db),              // Poisson 010: the y pass without double buffering

@@ -903,7 +903,8 @@ int x3d_ytile_transeq(x3d_backend *b, int dir, real_t *rhs, const real_t *u, con
 int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f[3], real_t nu,
                        const x3d_tdsops *der1st, const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd,
                        const x3d_tdsops *der2nd_sym, int acc, const real_t *const *upd_g, const x3d_tdsops *op_s,
-                       const x3d_tdsops *op_i, real_t scale, real_t omega, const real_t *ushift, bool *done);  // xscan.hip
+                       const x3d_tdsops *op_i, real_t scale, real_t omega, const real_t *ushift, bool *done,
+                       bool xinv = false);  // xscan.hip
 // xdir.hip
 int x3d_xwide_transeq3_upd(x3d_backend *b, real_t *const r[3], real_t *const f[3], real_t nu, const x3d_tdsops *der1st,
                            const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym,
@@ -1048,6 +1049,28 @@ extern "C" int x3d_tds_solve_xfft(x3d_backend *b, real_t *du, const real_t *u, c
     X3D_REQUIRE(du != u, "x3d_tds_solve_xfft: du and u must be distinct blocks");
     if (int rc = check_len(b, t, X3D_DIR_X, "tds_solve_xfft")) return rc;
     return x3d_xscan_tds_xfft(b, du, u, t);
+}
+
+// x tds_solve, accumulating, of a field that arrives still transformed along x, packed half-complex (include/x3d2_hip.h;
+// the kernel: csrc/xscan.hip k_xscan_tds_ixfft)
+bool x3d_xscan_tds_ixfft_ok(const x3d_backend *b, const x3d_tdsops *t);
+int x3d_xscan_tds_ixfft(x3d_backend *b, real_t *du, const real_t *g, const x3d_tdsops *t, real_t scale);
+extern "C" int x3d_tds_solve_ixfft_ok(x3d_backend *b, const x3d_tdsops *t, int *ok)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(b && t && ok, "x3d_tds_solve_ixfft_ok: null argument");
+    *ok = x3d_xscan_tds_ixfft_ok(b, t) ? 1 : 0;
+    return 0;
+}
+extern "C" int x3d_tds_solve_ixfft(x3d_backend *b, real_t *du, const real_t *g, const x3d_tdsops *t, real_t scale)
+{
+    X3D_RANGE(__func__);
+    if (b) X3D_LAZY_SYNC(b);
+    X3D_LAZY_EAGER(b);
+    X3D_REQUIRE(b && du && g && t, "x3d_tds_solve_ixfft: null argument");
+    X3D_REQUIRE(du != g, "x3d_tds_solve_ixfft: du and g must be distinct blocks");
+    if (int rc = check_len(b, t, X3D_DIR_X, "tds_solve_ixfft")) return rc;
+    return x3d_xscan_tds_ixfft(b, du, g, t, scale);
 }
 
 int x3d_ytile_tds_pair(x3d_backend *b, int dir, int mode, real_t *out1, real_t *out2, const real_t *in1, const real_t *in2,
@@ -1501,6 +1524,47 @@ extern "C" int x3d_transeq_x_update(x3d_backend *b, real_t *du, real_t *dv, real
                                             nullptr, &ok))
             return rc;
     }
+    *done = ok ? 1 : 0;
+    return 0;
+}
+
+// x3d_transeq_x_update for gradients that arrive still transformed along x, packed half-complex (round 7: the z-first 000
+// solve without its inverse x pass): each pencil is inverted inside the kernel before its circulant solve
+// (k_xscan_transeq2x3<XINV>, csrc/xscan.hip).  *done = 0: not served, nothing was done (issue x3d_tds_solve_ixfft x 3 and
+// x3d_transeq).  Bit-identical to that sequence.  x3d_transeq_x_update_xinv_ok: *ok = 1 when both operators are ones the
+// form takes (x3d_tds_solve_ixfft_ok)
+extern "C" int x3d_transeq_x_update_xinv_ok(x3d_backend *b, const x3d_tdsops *op_u, const x3d_tdsops *op_vw, int *ok)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(b && op_u && op_vw && ok, "x3d_transeq_x_update_xinv_ok: null argument");
+    *ok = b->sw.x_tq3 && b->sw.x_circ && x3d_xscan_tds_ixfft_ok(b, op_u) && x3d_xscan_tds_ixfft_ok(b, op_vw) ? 1 : 0;
+    return 0;
+}
+extern "C" int x3d_transeq_x_update_xinv(x3d_backend *b, real_t *du, real_t *dv, real_t *dw, real_t *u, real_t *v, real_t *w,
+                                         real_t nu, const x3d_tdsops *der1st, const x3d_tdsops *der1st_sym,
+                                         const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym, const real_t *gu,
+                                         const real_t *gv, const real_t *gw, const x3d_tdsops *op_u,
+                                         const x3d_tdsops *op_vw, real_t scale, int *done)
+{
+    X3D_RANGE(__func__);
+    if (b) X3D_LAZY_SYNC(b);
+    X3D_LAZY_EAGER(b);
+    X3D_REQUIRE(b && du && dv && dw && u && v && w && der1st && der1st_sym && der2nd && der2nd_sym && gu && gv && gw &&
+                    op_u && op_vw && done,
+                "x3d_transeq_x_update_xinv: null argument");
+    *done = 0;
+    if (int rc = transeq_check(b, X3D_DIR_X, der1st, der1st_sym, der2nd)) return rc;
+    if (int rc = check_len(b, op_u, X3D_DIR_X, "transeq_x_update_xinv")) return rc;
+    if (int rc = check_len(b, op_vw, X3D_DIR_X, "transeq_x_update_xinv")) return rc;
+    real_t *r[3] = {du, dv, dw};
+    const real_t *f[3] = {u, v, w}, *g[3] = {gu, gv, gw};
+    for (int c = 0; c < 3; c++)
+        for (int k = 0; k < 3; k++)
+            X3D_REQUIRE(r[c] != f[k] && r[c] != g[k] && f[c] != g[k], "x3d_transeq_x_update_xinv: arguments alias");
+    bool ok = false;
+    if (int rc = x3d_xscan_transeq3(b, r, f, nu, der1st, der1st_sym, der2nd, der2nd_sym, 0, g, op_u, op_vw, scale, 0.0,
+                                    nullptr, &ok, true))
+        return rc;
     *done = ok ? 1 : 0;
     return 0;
 }

@@ -255,6 +255,40 @@ __global__ void __launch_bounds__(512, 4) k_xscan_tds_xfft(real_t *__restrict__ 
     }
 }
 
+// ---------------------------------------------------------------- inverse x transform + accumulating tds_solve (round 7)
+// The way back: between the spectral division and the last three x operators of gradient_c2v (the y inverse of the middle,
+// the z pair with its complex-to-real z transform, the y pair and the single y operator) everything is again x-independent
+// and real-linear column by column, so the solve's inverse x pass need not run either: the three gradient fields then
+// arrive here as pack(rfft_x(field)), and the pencil is inverted on the wave that holds it (irfft512_packed_wave,
+// fft512_core.h: 512 x the rows, the scaling of k_c2c512_x<+1>).  From the rows on this is k_xscan_tds<8, true, 3>: the
+// circulant solve and du = old + scale * r, same bits.  g is read 16 bytes per lane, 1 KB contiguous per instruction, the
+// next pencil's a pencil ahead.  LDS as in k_xscan_tds_xfft.
+__global__ void __launch_bounds__(512, 4) k_xscan_tds_ixfft(real_t *__restrict__ du, const real_t *__restrict__ g, int np,
+                                                            long pitch, real_t scale, CircOp co,
+                                                            const real2_t *__restrict__ twg)
+{
+    constexpr int Q = 8;
+    extern __shared__ real2_t xf[];  // [8][FP256] + 256 twiddles
+    real2_t *__restrict__ tws = xf + 8 * FP256;
+    if (threadIdx.x < 256) tws[threadIdx.x] = twg[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    real2_t *__restrict__ pen = xf + wave * FP256;
+    const int nwaves = gridDim.x * (blockDim.x >> 6);
+    const int p0 = blockIdx.x * (blockDim.x >> 6) + wave;
+    real2_t ng[4];  // next pencil's packed columns, in flight while this one is inverted and solved
+    if (p0 < np) load_packed(ng, g + (long)p0 * pitch, lane);
+    for (int p = p0; p < np; p += nwaves) {
+        real_t b[Q], w[Q + 8], r[Q];
+        irfft512_packed_wave(ng, b, pen, tws, lane);
+        if (p + nwaves < np) load_packed(ng, g + (long)(p + nwaves) * pitch, lane);
+        window_from_body<Q>(w, b, lane);
+        circ_solve<Q, true>(w, r, co, lane);
+        store_rows_q8<true>(du + (long)p * pitch, lane, r, scale);
+    }
+}
+
 // ---------------------------------------------------------------- tds_solve of a field that is still to be formed
 // The first x operators of the pressure correction act on the velocity the RK / AB stage has just produced
 // (y = base + sum c_k x_k, src/time_integrator.f90:166-282 -> divergence_v2c, src/vector_calculus.f90:160-175).
@@ -554,15 +588,29 @@ struct XUpd {
 
 // CIRC (round 6; uniform grid, NARROW): every operator in the circulant form (circ_solve; cc[0..3] = der1st, der2nd, op_s,
 // op_i) -- no lane tables, no LDS
-template <int Q, bool ACC, bool NARROW, bool UPD, bool CHN = false, bool CIRC = false>  // CHN: the channel case's extras (XUpd)
+// XINV (round 7; UPD && CIRC, Q = 8): upd.g[c] arrive still transformed along x, packed half-complex (the z-first 000 solve
+// without its inverse x pass, k_xscan_tds_ixfft above): each pencil of the pair is inverted first (irfft512_packed_wave,
+// the two taking turns in the wave's one LDS region: 8 x FP256 + 256 twiddles = 40 KB) and enters the circulant solve as
+// before -- the bits of k_xscan_tds_ixfft.  The packed columns are requested a component ahead (ga, gb: 32 VGPRs).
+template <int Q, bool ACC, bool NARROW, bool UPD, bool CHN = false, bool CIRC = false, bool XINV = false>  // CHN: the channel case's extras (XUpd)
 __global__ void __launch_bounds__(512)
     k_xscan_transeq2x3(real_t *__restrict__ rhs0, real_t *__restrict__ rhs1, real_t *__restrict__ rhs2, real_t *u0,
                        real_t *u1, real_t *u2, XOp tD1, XOp tD2, int np, long pitch, real_t nu, XUpd upd, XOp tS,
-                       XOp tI, Circ4 cc)
+                       XOp tI, Circ4 cc, const real2_t *__restrict__ twg = nullptr)
 {
     extern __shared__ real_t lt[];
     constexpr int LNF = LT_N(Q) * 64, LNC = LT_NC(Q) * 64, L1N = UPD ? LNC : LNF;
     static_assert(!CIRC || NARROW, "CIRC: 5-tap stencils");
+    static_assert(!XINV || (UPD && CIRC && Q == 8 && !CHN), "XINV: the circulant UPD form on 512-row pencils");
+    real2_t *__restrict__ xpen = nullptr;
+    const real2_t *__restrict__ tws = nullptr;
+    if constexpr (XINV) {
+        real2_t *__restrict__ xf = reinterpret_cast<real2_t *>(lt);  // [8][FP256] + 256 twiddles
+        if (threadIdx.x < 256) xf[8 * FP256 + threadIdx.x] = twg[threadIdx.x];
+        __syncthreads();
+        tws = xf + 8 * FP256;
+        xpen = xf + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * FP256;
+    }
     if constexpr (!CIRC) {
         for (int i = threadIdx.x; i < L1N; i += blockDim.x) lt[i] = tD1.TL[i];
         for (int i = threadIdx.x; i < LNF; i += blockDim.x) lt[L1N + i] = tD2.TL[i];
@@ -581,9 +629,14 @@ __global__ void __launch_bounds__(512)
     const real_t *__restrict__ l1 = lt, *__restrict__ l3 = lt + L1N;
     real_t na[Q], nb[Q];  // the rows needed next (next component's field, or the next pair's u0)
     const int pstart = 2 * (blockIdx.x * (blockDim.x >> 6) + wave);
+    real2_t ga[XINV ? 4 : 1], gb[XINV ? 4 : 1];  // XINV: the packed gradient columns needed next
     if (pstart < np) {
         load_body<Q>(na, u0 + (long)pstart * pitch, lane);
         load_body<Q>(nb, u0 + (long)(pstart + 1) * pitch, lane);
+        if constexpr (XINV) {
+            load_packed(ga, upd.g[0] + (long)pstart * pitch, lane);
+            load_packed(gb, upd.g[0] + (long)(pstart + 1) * pitch, lane);
+        }
     }
     for (int p = pstart; p < np; p += 2 * nwaves) {
         V2 cb[Q];
@@ -606,13 +659,27 @@ __global__ void __launch_bounds__(512)
                 }
                 if constexpr (UPD) {
                     // u_c += scale * tds_solve(g_c), arithmetic of k_xscan_tds<ACC>: old + scale * r
-                    const real_t *gsrc = (c == 0 ? upd.g[0] : (c == 1 ? upd.g[1] : upd.g[2])) + (long)p * pitch;
-                    real_t ga[Q], gb[Q];
-                    load_body<Q>(ga, gsrc, lane);
-                    load_body<Q>(gb, gsrc + pitch, lane);
                     V2 g2[Q], wg[Q + 8], X[Q], du1, xn;
+                    if constexpr (XINV) {
+                        real_t ra_[Q], rb_[Q];
+                        irfft512_packed_wave(ga, ra_, xpen, tws, lane);
+                        irfft512_packed_wave(gb, rb_, xpen, tws, lane);
 #pragma unroll
-                    for (int q = 0; q < Q; q++) g2[q] = V2{ga[q], gb[q]};
+                        for (int q = 0; q < Q; q++) g2[q] = V2{ra_[q], rb_[q]};
+                        const real_t *gn = c == 0 ? upd.g[1] + (long)p * pitch : (c == 1 ? upd.g[2] + (long)p * pitch
+                                                                                    : upd.g[0] + (long)(pn < np ? pn : p) * pitch);
+                        if (c < 2 || pn < np) {
+                            load_packed(ga, gn, lane);
+                            load_packed(gb, gn + pitch, lane);
+                        }
+                    } else {
+                        const real_t *gsrc = (c == 0 ? upd.g[0] : (c == 1 ? upd.g[1] : upd.g[2])) + (long)p * pitch;
+                        real_t ga_[Q], gb_[Q];
+                        load_body<Q>(ga_, gsrc, lane);
+                        load_body<Q>(gb_, gsrc + pitch, lane);
+#pragma unroll
+                        for (int q = 0; q < Q; q++) g2[q] = V2{ga_[q], gb_[q]};
+                    }
                     window_from_body<Q, V2>(wg, g2, lane);
                     if constexpr (CIRC) {
                         if (c == 0) circ_solve<Q, NARROW, V2>(wg, X, cc.o[2], lane);
@@ -1642,6 +1709,26 @@ int x3d_xscan_tds_xfft(x3d_backend *b, real_t *du, const real_t *u, const x3d_td
     return 0;
 }
 
+// inverse x transform + accumulating tds_solve (k_xscan_tds_ixfft): the gates of x3d_xscan_tds_xfft_ok, and X3D_NO_XFFT_GRAD
+bool x3d_xscan_tds_ixfft_ok(const x3d_backend *b, const x3d_tdsops *t)
+{
+    return x3d_xscan_tds_xfft_ok(b, t) && !b->sw.no_xfft_grad;
+}
+int x3d_xscan_tds_ixfft(x3d_backend *b, real_t *du, const real_t *g, const x3d_tdsops *t, real_t scale)
+{
+    X3D_REQUIRE(x3d_xscan_tds_ixfft_ok(b, t), "x3d_tds_solve_ixfft: not on offer for this operator (x3d_tds_solve_ixfft_ok)");
+    if (int rc = x3d_fft512_init()) return rc;
+    const int np = b->ny * b->nz;
+    const size_t lds = sizeof(real2_t) * (8 * FP256 + 256);
+    int blocks = (np + 7) / 8;
+    blocks = blocks > 1024 ? 1024 : blocks;  // (as x3d_xscan_tds_xfft)
+    ProfScope ps(b, X3D_K_TDS_FWD, X3D_DIR_X);
+    hipLaunchKernelGGL(k_xscan_tds_ixfft, dim3(blocks), dim3(512), lds, b->stream, du, g, np, (long)b->nxp, scale, t->circ,
+                       x3d_fft512_twiddles());
+    X3D_HIP(hipGetLastError());
+    return 0;
+}
+
 template <int Q, bool SAME, bool ACC, int FAST>
 static int launch_transeq(x3d_backend *b, real_t *rhs, const real_t *u, const real_t *conv, real_t nu,
                           const x3d_tdsops *t1, const x3d_tdsops *t2, const x3d_tdsops *t3, int np, int blocks,
@@ -2098,13 +2185,16 @@ int x3d_ytile_transeq3_epi(x3d_backend *b, int dir, real_t *const r[3], const re
 }
 
 // transeq_x in one launch (k_xscan_transeq2x3); f[0] is the advecting component.  upd_g != null: the pending
-// correction f[c] += scale * tds_solve(upd_g[c]) with op_s (c = 0) / op_i (c = 1, 2) is applied first (UPD form)
+// correction f[c] += scale * tds_solve(upd_g[c]) with op_s (c = 0) / op_i (c = 1, 2) is applied first (UPD form);
+// xinv: upd_g[c] are still transformed along x, packed half-complex (XINV form: not served unless both operators pass
+// x3d_xscan_tds_ixfft_ok and every operator is in the circulant form)
 int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f[3], real_t nu,
                        const x3d_tdsops *der1st, const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd,
                        const x3d_tdsops *der2nd_sym, int acc, const real_t *const *upd_g, const x3d_tdsops *op_s,
-                       const x3d_tdsops *op_i, real_t scale, real_t omega, const real_t *ushift, bool *done)
+                       const x3d_tdsops *op_i, real_t scale, real_t omega, const real_t *ushift, bool *done, bool xinv)
 {
     *done = false;
+    if (xinv && !(upd_g && !acc && x3d_xscan_tds_ixfft_ok(b, op_s) && x3d_xscan_tds_ixfft_ok(b, op_i))) return 0;
     if ((omega != 0.0 || ushift) && (acc || upd_g)) return 0;
     if (!b->sw.x_tq3 || !x3d_xscan_fast_ok(der1st, der1st_sym, der2nd) || !x3d_xscan_fast_ok(der1st_sym, der1st, der2nd_sym)) return 0;
     if (der1st->tl_hash != der1st_sym->tl_hash || der2nd->tl_hash != der2nd_sym->tl_hash) return 0;
@@ -2120,8 +2210,13 @@ int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f
     const bool narrow = stencil_narrow(der1st) && stencil_narrow(der2nd) && (!upd || (stencil_narrow(op_s) && stencil_narrow(op_i)));
     const bool circ = b->sw.x_circ && narrow && der1st->circ_ok && der1st_sym->circ_ok && der2nd->circ_ok && der2nd_sym->circ_ok &&
                       (!upd || (op_s->circ_ok && op_i->circ_ok));
-    const size_t lds = circ ? 0 : sizeof(real_t) * 64 * (upd ? 3 * LT_NC(Q) + LT_N(Q) : 2 * LT_N(Q));
+    if (xinv && !(circ && Q == 8)) return 0;
+    const size_t lds = xinv ? sizeof(real2_t) * (8 * FP256 + 256)
+                            : (circ ? 0 : sizeof(real_t) * 64 * (upd ? 3 * LT_NC(Q) + LT_N(Q) : 2 * LT_N(Q)));
     if (lds > 160 * 1024) return 0;
+    if (xinv) {
+        if (int rc = x3d_fft512_init()) return rc;
+    }
     const int blocks = x3d_persistent_blocks(b, (np / 2 + 7) / 8);
     XUpd xu{};
     if (upd) { xu.g[0] = upd_g[0]; xu.g[1] = upd_g[1]; xu.g[2] = upd_g[2]; xu.scale = scale; }
@@ -2133,7 +2228,7 @@ int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f
         X3D_LDS_OPTIN(b, (k_xscan_transeq2x3<Q_, A_, N_, U_, C_, X_>));                                         \
         hipLaunchKernelGGL((k_xscan_transeq2x3<Q_, A_, N_, U_, C_, X_>), dim3(blocks), dim3(512), lds, b->stream, r[0], r[1], \
                            r[2], (real_t *)f[0], (real_t *)f[1], (real_t *)f[2], xop_of(der1st), xop_of(der2nd), np,  \
-                           (long)b->nxp, nu, xu, xop_of(ts), xop_of(ti), c4);                                   \
+                           (long)b->nxp, nu, xu, xop_of(ts), xop_of(ti), c4, nullptr);                          \
     } while (0)
 #define GO(Q_, A_, N_, U_, C_) do { if ((N_) && circ) GOX(Q_, A_, true, U_, C_, true); else GOX(Q_, A_, N_, U_, C_, false); } while (0)
 #define GOU(Q_, A_, N_) do { if (upd) GO(Q_, A_, N_, true, false); else GO(Q_, A_, N_, false, false); } while (0)
@@ -2146,7 +2241,12 @@ int x3d_xscan_transeq3(x3d_backend *b, real_t *const r[3], const real_t *const f
     } while (0)
     {
         ProfScope ps(b, X3D_K_TRANSEQ_FWD, X3D_DIR_X);
-        if (Q == 8) GOA(8); else GOA(4);
+        if (xinv) {
+            X3D_LDS_OPTIN(b, (k_xscan_transeq2x3<8, false, true, true, false, true, true>));
+            hipLaunchKernelGGL((k_xscan_transeq2x3<8, false, true, true, false, true, true>), dim3(blocks), dim3(512), lds,
+                               b->stream, r[0], r[1], r[2], (real_t *)f[0], (real_t *)f[1], (real_t *)f[2], xop_of(der1st),
+                               xop_of(der2nd), np, (long)b->nxp, nu, xu, xop_of(ts), xop_of(ti), c4, x3d_fft512_twiddles());
+        } else if (Q == 8) GOA(8); else GOA(4);
     }
 #undef GOA
 #undef GON

@@ -18,7 +18,9 @@
 // rotations cancel pairwise: |b - i a| = 1, so any consistent choice gives the result up to rounding).
 // Round 7: where the divergence's x operators have transformed along x already (k_xscan_tds_xfft, csrc/xscan.hip: rows
 // packed half-complex) the forward x pass is not run, the y pass takes the reciprocal wave numbers of the packed columns and
-// the inverse x pass untangles first (x3d_poisson_zfirst_middle_xpacked): 4.5 passes.
+// the inverse x pass untangles first (x3d_poisson_zfirst_middle_xpacked): 4.5 passes.  Where the gradient's last x
+// operators invert the transform themselves (k_xscan_tds_ixfft, k_xscan_transeq2x3<XINV>) the inverse x pass is not run
+// either (x3d_poisson_zfirst_middle_xpacked2): 2.5 passes.
 #include <vector>
 
 #include "fft_util.h"
@@ -390,6 +392,32 @@ extern "C" int x3d_poisson_zfirst_middle_xpacked(x3d_poisson *p)
     if (int rc = zh_table(p, true, &rw)) return rc;
     if (int rc = x3d_fft512_run_zh(p->b, p->c, ZH_PX, 0, 257, rw, p->ab, p->nx, p->ny, p->nz)) return rc;
     return c2c_x<1, true>(p, 0, 257);
+}
+
+// ---- ... and for a gradient whose last x operators invert the x transform themselves (round 7: x3d_tds_solve_ixfft,
+// x3d_transeq_x_update_xinv, csrc/xscan.hip).  The y inverse of the middle, the z pair with its complex-to-real z transform
+// and the y operators after it are x-independent and real-linear column by column like everything before the division: the
+// packed columns A_k, B_k leave the z transform as Re G_k(z), Im G_k(z), the spectrum needs no x pass at all.  The middle
+// is the y pass alone: 2.5 passes over the spectrum.  X3D_NO_XFFT_GRAD=1 (or X3D_NO_XFFT_DIV=1): not on offer
+extern "C" int x3d_poisson_xfft_grad_ok(x3d_poisson *p, int *ok)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(p && ok, "x3d_poisson_xfft_grad_ok: null argument");
+    if (int rc = x3d_poisson_xfft_ok(p, ok)) return rc;
+    if (p->b->sw.no_xfft_grad) *ok = 0;
+    return 0;
+}
+extern "C" int x3d_poisson_zfirst_middle_xpacked2(x3d_poisson *p)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(p, "x3d_poisson_zfirst_middle_xpacked2: null argument");
+    int ok = 0;
+    if (int rc = x3d_poisson_xfft_grad_ok(p, &ok)) return rc;
+    X3D_REQUIRE(ok, "x3d_poisson_zfirst_middle_xpacked2: not on offer for this solver (x3d_poisson_xfft_grad_ok)");
+    X3D_LAZY_EAGER(p->b);
+    const real_t *rw;
+    if (int rc = zh_table(p, true, &rw)) return rc;
+    return x3d_fft512_run_zh(p->b, p->c, ZH_PX, 0, 257, rw, p->ab, p->nx, p->ny, p->nz);
 }
 
 // ---- proxy of a z-first solve whose middle the CALLER runs (include/x3d2_hip.h, x3d_poisson_create_proxy)

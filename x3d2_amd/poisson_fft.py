@@ -391,8 +391,21 @@ class HipPoissonFFT:
         _lib.check(self.backend.lib.x3d_poisson_xfft_ok(self.h, ctypes.byref(ok)))
         return bool(ok.value)
 
-    def zfirst_middle_xpacked(self):
-        _lib.check(self.backend.lib.x3d_poisson_zfirst_middle_xpacked(self.h))
+    def zfirst_middle_xpacked(self, out_packed=False):
+        if out_packed:
+            _lib.check(self.backend.lib.x3d_poisson_zfirst_middle_xpacked2(self.h))
+        else:
+            _lib.check(self.backend.lib.x3d_poisson_zfirst_middle_xpacked(self.h))
+
+    def xfft_grad_ok(self):
+        """... and leaves that spectrum packed along x for a gradient whose last x operators invert the transform
+        themselves (HipBackend.tds_apply_ixfft, transeq_x_update_xinv): zfirst_middle_xpacked(out_packed=True) is then
+        the y pass alone (X3D_NO_XFFT_GRAD=1 or X3D_NO_XFFT_DIV=1: never)"""
+        if not self.xfft_ok():
+            return False
+        ok = ctypes.c_int(0)
+        _lib.check(self.backend.lib.x3d_poisson_xfft_grad_ok(self.h, ctypes.byref(ok)))
+        return bool(ok.value)
 
     def zfirst_forward(self, f):
         _lib.check(self.backend.lib.x3d_poisson_zfirst_forward(self.h, f.ptr))

@@ -130,6 +130,15 @@ class Solver:
                               and not any(backend._decomposed(d) for d in (DIR_X, DIR_Y, DIR_Z))
                               and backend.tds_apply_xfft_ok(x.stagder_v2p) and backend.tds_apply_xfft_ok(x.interpl_v2p))
         self.n_xfft_div = 0                              # pressure corrections that took that form (tests)
+        # ... and its inverse x transform on the last three x operators of the gradient (k_xscan_tds_ixfft and
+        # k_xscan_transeq2x3<XINV>; X3D_NO_XFFT_GRAD=1: a pass of its own): asked once, for the solver, both accumulating
+        # operators and the x kernel that applies a deferred correction
+        self._xfft_grad = bool(self._xfft_div and getattr(pf, "xfft_grad_ok", lambda: False)()
+                               and backend.tds_apply_ixfft_ok(x.stagder_p2v) and backend.tds_apply_ixfft_ok(x.interpl_p2v)
+                               and backend.transeq_x_update_xinv_ok(x.stagder_p2v, x.interpl_p2v))
+        self.n_xfft_grad = 0                             # pressure corrections whose gradient stayed packed (tests)
+        self.pending_grad_packed = False                 # pending_grad's blocks are still transformed along x
+        self._grad_packed = False                        # (pressure_correction_fused -> _finish_pressure_correction)
         self.shift_request = None  # device scalar to add to u before transeq_x uses it (field_mean_shift)
         self.pending_walls = None  # wall fields to stamp on u, v, w inside the divergence's first kernels
         # (round 6) the case's next define_BC wants field_mean_shift(u, mean_request): taken along by the kernel that
@@ -291,7 +300,14 @@ class Solver:
             # rotation forcing where those were asked for (round 6: k_xwide_transeq3_upd; the shift's mean was then
             # taken of the uncorrected u, BaseCase.correction_deferrable)
             g, self.pending_grad = self.pending_grad, None
-            if rot != 0.0 or shift is not None:
+            packed, self.pending_grad_packed = self.pending_grad_packed, False
+            if packed:
+                # the gradient is still transformed along x (the z-first solve without its inverse x pass): the kernel
+                # inverts each pencil first; a shift or a rotation keeps its own sequence below
+                if rot == 0.0 and shift is None and \
+                        b.transeq_x_update_xinv(du, dv, dw, u, v, w, self.nu, x, g, x.stagder_p2v, x.interpl_p2v, -1.0):
+                    served = True
+            elif rot != 0.0 or shift is not None:
                 if not self.sw.no_rot_fused and \
                         b.transeq_x_update_rot(du, dv, dw, u, v, w, self.nu, x, g, x.stagder_p2v, x.interpl_p2v, -1.0, rot, shift):
                     served = True
@@ -301,7 +317,7 @@ class Solver:
             elif b.transeq_x_update(du, dv, dw, u, v, w, self.nu, x, g, x.stagder_p2v, x.interpl_p2v, -1.0):
                 served = True
             if not served:
-                self._apply_grad(g, u, v, w)
+                self._apply_grad(g, u, v, w, packed)
             for f in g:
                 b.allocator.release_block(f)
         if served:
@@ -472,9 +488,12 @@ class Solver:
             b.tds_apply(a2, t3, y.interpl_v2p, DIR_Y)
             # 000 solve at 512^3: z-first -- the z pairs on either side transform along z on their tiles, the divergence
             # and the pressure never exist as fields (csrc/zfirst.hip)
-            if self._zfirst and not want_p and self._zfirst_solve(a1, a2, t2, t3, xpacked=xfft):
+            # ... and with the x transform done by the divergence, the gradient's last x operators invert it: no x pass
+            xgrad = xfft and self._xfft_grad
+            if self._zfirst and not want_p and self._zfirst_solve(a1, a2, t2, t3, xpacked=xfft, xpacked_out=xgrad):
                 b.tds_pair(1, a1, a2, t2, None, y.interpl_p2v, y.stagder_p2v, DIR_Y)   # p_sx, dpdy_sx
                 b.tds_apply(t1, t3, y.interpl_p2v, DIR_Y)                              # dpdz_sx
+                self._grad_packed = xgrad
                 return self._finish_pressure_correction(u, v, w, (t1, t2, t3, a1, a2), defer_grad)
             if nil and not want_p and b.tds_pair_yperm(0, t2, None, a1, a2, z.interpl_v2p, z.stagder_v2p, nil):
                 div = t2  # (t2, t3 are free after the y stage) rows interleaved
@@ -520,19 +539,21 @@ class Solver:
                 b.tds_apply(t1, t3, y.interpl_p2v, DIR_Y)
         self._finish_pressure_correction(u, v, w, (t1, t2, t3, a1, a2), defer_grad)
 
-    def _zfirst_solve(self, a1, a2, t2, t3, xpacked=False):
+    def _zfirst_solve(self, a1, a2, t2, t3, xpacked=False, xpacked_out=False):
         """div = interpl_z(a1) + stagder_z(a2) ; p = poisson(div) ; t2 = interpl_z(p), t3 = stagder_z(p) with the z
         transforms of the 000 solve on the tiles of the two z pairs; False: not served for these operators, nothing done.
-        xpacked: a1, a2 are transformed along x already, packed half-complex (HipBackend.tds_apply_xfft)"""
+        xpacked: a1, a2 are transformed along x already, packed half-complex (HipBackend.tds_apply_xfft);
+        xpacked_out: t2, t3 stay so (no inverse x pass: HipBackend.tds_apply_ixfft inverts 512 x the field)"""
         b, z = self.backend, self.zdirps
         if xpacked:
             if not b.tds_pair_zfirst(0, None, None, a1, a2, z.interpl_v2p, z.stagder_v2p):
                 raise X3dError("pressure_correction: x-transformed operands, but the z-first pair declined the divergence")
-            b.poisson_fft.zfirst_middle_xpacked()
+            b.poisson_fft.zfirst_middle_xpacked(out_packed=xpacked_out)
             if not b.tds_pair_zfirst(1, t2, t3, None, None, z.interpl_p2v, z.stagder_p2v):
                 raise X3dError("pressure_correction: the z-first pair served the divergence but not the gradient")
             self.n_zfirst += 1
             self.n_xfft_div += 1
+            self.n_xfft_grad += 1 if xpacked_out else 0
             return True
         pipe = getattr(b.poisson_fft, "zfirst_solve_pipelined", None)
         if pipe is not None and not b._decomposed(DIR_Z) and \
@@ -552,14 +573,16 @@ class Solver:
         """velocity correction from (a1, a2, t1) = (dpdx_sx, dpdy_sx, dpdz_sx) -- the last x operators of gradient_c2v"""
         al = self.backend.allocator
         t1, t2, t3, a1, a2 = blocks
+        packed, self._grad_packed = self._grad_packed, False  # (the three blocks are still transformed along x)
         if (defer_grad and not self.sw.no_defer and not self.sw.no_defer_grad
                 and self.nspecies == 0):
             # the next sub-step's transeq_x applies the correction inside its own kernel (transeq_fused)
             self.pending_grad = (a1, a2, t1)
+            self.pending_grad_packed = packed
             for f in (t2, t3):
                 al.release_block(f)
             return
-        self._apply_grad((a1, a2, t1), u, v, w)
+        self._apply_grad((a1, a2, t1), u, v, w, packed)
         for f in (t1, t2, t3, a1, a2):
             al.release_block(f)
 
@@ -609,9 +632,15 @@ class Solver:
         b.tds_jobs(DIR_Z, jz, yperm=nil)
         b.tds_jobs(DIR_Y, jy)
 
-    def _apply_grad(self, g, u, v, w):
-        """velocity correction, src/solver.f90:731-733 folded into the last x operators of gradient_c2v"""
+    def _apply_grad(self, g, u, v, w, packed=False):
+        """velocity correction, src/solver.f90:731-733 folded into the last x operators of gradient_c2v; packed: g is
+        still transformed along x and the operators invert it first (csrc/xscan.hip k_xscan_tds_ixfft)"""
         b, x = self.backend, self.xdirps
+        if packed:
+            b.tds_apply_ixfft(u, g[0], x.stagder_p2v, -1.0)
+            b.tds_apply_ixfft(v, g[1], x.interpl_p2v, -1.0)
+            b.tds_apply_ixfft(w, g[2], x.interpl_p2v, -1.0)
+            return
         b.tds_apply(u, g[0], x.stagder_p2v, DIR_X, accumulate=True, scale=-1.0)
         b.tds_apply(v, g[1], x.interpl_p2v, DIR_X, accumulate=True, scale=-1.0)
         b.tds_apply(w, g[2], x.interpl_p2v, DIR_X, accumulate=True, scale=-1.0)
@@ -631,7 +660,8 @@ class Solver:
         """apply a pending velocity correction now (anything that reads u, v, w before the next transeq)"""
         if self.pending_grad is not None:
             g, self.pending_grad = self.pending_grad, None
-            self._apply_grad(g, self.u, self.v, self.w)
+            packed, self.pending_grad_packed = self.pending_grad_packed, False
+            self._apply_grad(g, self.u, self.v, self.w, packed)
             for f in g:
                 self.backend.allocator.release_block(f)
 
