@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -70,6 +70,16 @@ restored before every timed call: the kernel works in place), next to the fused 
 write stream) in the same process, and the gate t_stress <= 1.25 (128 / 168) t_stats_update; (b) a whole Les.add next to a
 whole Diagnostics sample, wall clock around a device sync; (c) 20 fused RK3 TGV steps with and without the model: added wall
 time per step (no gate).  The lines are appended to profiles/les.jsonl.
+
+Family "particles" (--snap-n^3 = 512^3, median of --stat-iters with the quartiles as spread; not part of "all"), on the velocity
+of a fused TGV run three steps old: (a) x3d_particles_advance (HIP events) for 2^16, 2^20 and 2^22 particles, orders 2 and 4,
+tracers and inertial, straight after seed_uniform (random order) and straight after a sort, in particles per second and in the
+field bytes the stencils ask for (order^3 x 3 values per particle); beside them the sort (keys + radix sort + gather: the first
+one from random order as one sample, then the median on the sorted state) and x3d_probe_sample for 4096 probes; (b) the choice
+of the default sort_every: 64 steps with 2^20 order-4 tracers at sort_every 0, 1, 8 and 64, HIP events around Particles.update
+(advance and the sorts that fall due), mean per step; (c) 20 fused RK3 steps with nothing attached, with Probes at every step
+(which gives up the more=True deferral as the particles do) and with 2^20 order-4 tracers (never sorted): wall time.  No gate.  The lines are
+appended to profiles/particles.jsonl.
 """
 import argparse
 import json
@@ -985,13 +995,110 @@ def bench_les(args):
               "ms_per_step_without": res[None] / 20.0, "added_ms_per_step": (res[model] - res[None]) / 20.0})
 
 
+def bench_particles(args):
+    """one JSON line per measurement of the "particles" family, printed and appended to profiles/particles.jsonl"""
+    import ctypes
+    import tempfile
+
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.particles import Particles, ParticlesConfig, seed_uniform
+    from x3d2_amd.probes import Probes, ProbesConfig
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    tmp = tempfile.mkdtemp(prefix="x3d_particles_")
+    out_path = os.path.join(ROOT, "profiles", "particles.jsonl")
+
+    def emit(row):
+        row = dict({"family": "particles", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    # (a) the launches alone, on the velocity of a TGV run three steps old
+    case = make_tgv(n, fused=True)
+    s = case.solver
+    b = s.backend
+    case.run(n_iters=3)
+    for log2 in (16, 20, 22):
+        npart = 1 << log2
+        x0 = seed_uniform(s.mesh, npart, seed=1)
+        for order in (2, 4):
+            for tau in (0.0, 20.0 * float(s.dt)):
+                p = Particles(s, ParticlesConfig(x0, order=order, tau_p=tau))
+                kind = "inertial" if tau else "tracers"
+                fetched = order ** 3 * 3 * rb  # field bytes a particle's stencils ask for
+                for state in ("random order", "sorted"):
+                    if state == "sorted":
+                        _lib.check(b.lib.x3d_timer_start(b.h))
+                        p.sort()
+                        ms = ctypes.c_float()
+                        _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+                        emit({"op": "x3d_particles_sort from random order: keys + radix sort + gather (one sample)", "particles": npart,
+                              "order": order, "kind": kind, "ms": ms.value})
+                    t = spread(timed_events(args, b, lambda: p.advance(s.u, s.v, s.w, s.dt)))
+                    emit(dict({"op": "x3d_particles_advance, %s" % state, "particles": npart, "order": order, "kind": kind,
+                               "particles_per_s": npart / t["ms_median"] * 1e3, "fetched_bytes_per_particle": fetched,
+                               "fetched_GBs": npart * fetched / t["ms_median"] / 1e6}, **t))
+                t = spread(timed_events(args, b, p.sort))
+                emit(dict({"op": "x3d_particles_sort of a sorted state: keys + radix sort + gather", "particles": npart, "order": order,
+                           "kind": kind}, **t))
+                del p
+    pts = seed_uniform(s.mesh, 4096, seed=2)
+    pr = Probes(s, ProbesConfig(pts, prefix=os.path.join(tmp, "probes")))
+    row = torch.zeros(3 * 4096, dtype=torch.float64, device=b.device)
+    t = spread(timed_events(args, b, lambda: b.probe_sample(pr.h, s.u, s.v, s.w, row.data_ptr())))
+    emit(dict({"op": "x3d_probe_sample on the same box, 4096 probes"}, **t))
+    del case, s, b, pr, row
+    torch.cuda.empty_cache()
+    # (b) the default sort_every: 64 steps with 2^20 tracers seeded in random order; HIP events around Particles.update
+    for m in (0, 1, 8, 64):
+        case = make_tgv(n, fused=True)
+        s = case.solver
+        b = s.backend
+        p = Particles(s, ParticlesConfig(seed_uniform(s.mesh, 1 << 20, seed=1), sort_every=m))
+        ms, times = ctypes.c_float(), []
+        for it in range(1, 65):
+            case.step(it)
+            s.current_iter = it
+            s.flush_grad()
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            p.update(it)
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            times.append(ms.value)
+        emit({"op": "Particles.update over 64 fused TGV steps, 2^20 order-4 tracers", "sort_every": m,
+              "particle_ms_per_step": float(np.mean(times)), "ms_median": float(np.median(times)), "ms_max": float(max(times))})
+        del case, s, b, p
+        torch.cuda.empty_cache()
+    # (c) 20 steps: nothing attached (the parent's path), probes at every step (gives up the deferral too), 2^20 order-4 tracers
+    res = {}
+    for what in ("nothing", "probes", "particles"):
+        case = make_tgv(n, fused=True)
+        s = case.solver
+        if what == "probes":
+            case.probes = Probes(s, ProbesConfig(pts, prefix=os.path.join(tmp, "probes20")))
+        if what == "particles":
+            case.particles = Particles(s, ParticlesConfig(seed_uniform(s.mesh, 1 << 20, seed=1), sort_every=0))
+        case.run(n_iters=3)
+        s.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        s.backend.sync()
+        res[what] = (time.perf_counter() - t0) * 1e3
+        del case, s
+        torch.cuda.empty_cache()
+    for what in ("probes", "particles"):
+        emit({"op": "TGV, fused, RK3: 20 steps, %s" % what, "wall_ms_without": res["nothing"], "wall_ms_with": res[what],
+              "ms_per_step_without": res["nothing"] / 20.0, "added_ms_per_step": (res[what] - res["nothing"]) / 20.0})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "loads",
-                                                               "budgets", "les"))
+                                                               "budgets", "les", "particles"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -1014,7 +1121,9 @@ def main():
         bench_loads(args)
     if args.family == "les":
         bench_les(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les"):
+    if args.family == "particles":
+        bench_particles(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les", "particles"):
         return
     import torch
     from x3d2_amd import Mesh

@@ -1013,6 +1013,58 @@ int x3d_probe_sample(x3d_backend *b, const x3d_probe *p, const x3d_real *u, cons
                      const int dims[3], double *row_dev);
 int x3d_probe_destroy(x3d_probe *p);
 
+/* ---- Lagrangian particles (csrc/particles.hip).  Not in the reference: this project's own addition.  Up to 2^24 points that
+ * follow the fluid (tau = 0: tracers, v = u(x)) or lag behind it (tau > 0: dv/dt = (u(x) - v) / tau + g), interpolated from the
+ * VERT blocks u, v, w with piecewise Lagrange polynomials of order 2 (two nodes per direction) or 4 (four; one-sided next to a
+ * wall, wrapped in a periodic direction) on the ACTUAL vertex coordinates, and advanced with second-order Adams-Bashforth on
+ * values stored with the particle.  One rank: the tables are the backend's own (global = local) vertices.  The state is double
+ * in both flavours, structure-of-arrays, rows of n values: x, v, a = u(x), the previous v (3 each) and, with tau > 0, F and the
+ * previous F (3 each): 12 or 18 rows, then id and status (int; 1 alive, 0 absorbed by a wall, 2 its position stopped being
+ * finite).  Every launch is ordered on the backend's stream behind a queue of the deferred-execution layer; only download and
+ * upload wait for the host.  No atomics; a particle that is not alive loads nothing.  A bad argument (null, n or m out of
+ * range, a bad order, input that is not finite, a position outside [first, last vertex] of a non-periodic direction, another
+ * backend's handle, dims outside the block or other than the vertices the particles were created for) is an error and
+ * launches nothing. */
+#define X3D_PARTICLES_MAX (1 << 24)
+enum { X3D_PARTICLES_REFLECT = 0, X3D_PARTICLES_ABSORB = 1 };
+typedef struct x3d_particles x3d_particles;
+typedef struct x3d_particles_params {
+    int n, order, wall;      /* 1 <= n <= X3D_PARTICLES_MAX; 2 or 4; X3D_PARTICLES_* */
+    double tau, g[3];        /* response time (0: tracers) and gravity */
+    int periodic[3];         /* per direction: wraps around L */
+    int uniform[3];          /* per direction: equidistant vertices (the cell is then guessed and corrected against the table) */
+    double L[3];             /* the period of a periodic direction */
+    const double *coords[3]; /* host tables of the backend's nx, ny, nz vertex coordinates, ascending; read once */
+} x3d_particles_params;
+/* x0[3][n], v0[3][n] (or NULL: the fluid's velocity at x0): host arrays, read once.  Not in the reference. */
+int x3d_particles_create(x3d_backend *b, const x3d_particles_params *prm, const double *x0, const double *v0, x3d_particles **out);
+int x3d_particles_destroy(x3d_particles *p); /* not in the reference */
+/* a = u(x); tracers v = a; inertial v = v0 (or a), F = (a - v) / tau + g; the next advance is a first one.  One launch.  Not in
+ * the reference. */
+int x3d_particles_prime(x3d_backend *b, x3d_particles *p, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                        const int dims[3]);
+/* one launch: x += dt (c1 v + c0 v_prev) [v += dt (c1 F + c0 F_prev)], (c1, c0) = (1, 0) on the first advance after a prime and
+ * (1.5, -0.5) afterwards and after an upload that carries its history; periodic wrap, wall rule, a = u(x) from the fields
+ * handed in, new v [F], history rotated.  Not in the reference. */
+int x3d_particles_advance(x3d_backend *b, x3d_particles *p, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                          const int dims[3], double dt);
+/* one launch: out_dev[3][m] = (u, v, w) at the points pts_dev[3][m] (device arrays) with the particles' order and tables; a
+ * periodic coordinate is wrapped, any other brought into [first, last vertex]; a point that is not finite gives NaN.  Not in the
+ * reference. */
+int x3d_particles_interpolate(x3d_backend *b, const x3d_particles *p, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                              const int dims[3], const double *pts_dev, int m, double *out_dev);
+/* order the state by the cell index (k ny + j) nx + i (uint32; particles that are not alive last): one key launch, rocPRIM's
+ * stable radix_sort_pairs in storage taken at creation, one gather launch of every row into the second set; the sets swap.  Not
+ * in the reference. */
+int x3d_particles_sort(x3d_backend *b, x3d_particles *p);
+/* one launch: x, v, a (9 rows of n doubles), id, status (2 rows of n ints) densely into dst_dev (80 n bytes, 8-byte aligned),
+ * in device order; waits on the device for a copy out of dst_dev that x3d_snapshot_copy_async started.  Not in the reference. */
+int x3d_particles_pack(x3d_backend *b, const x3d_particles *p, void *dst_dev, long capacity);
+/* the whole state to / from host arrays (rows[12 or 18][n], id[n], status[n]) in device order; both wait for the stream.  upload
+ * takes any order of the particles (id a permutation of 0..n-1) and checks what create checks.  Not in the reference. */
+int x3d_particles_download(x3d_backend *b, const x3d_particles *p, double *rows, int *id, int *status, int *has_history);
+int x3d_particles_upload(x3d_backend *b, x3d_particles *p, const double *rows, const int *id, const int *status, int has_history);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -279,6 +279,15 @@ PROTOTYPES = {
     "x3d_probe_create": (I, [VP, c_int_p, I, c_int_p, I, ctypes.POINTER(VP)]),
     "x3d_probe_sample": (I, [VP, VP, VP, VP, VP, c_int_p, VP]),
     "x3d_probe_destroy": (I, [VP]),
+    "x3d_particles_create": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(VP)]),
+    "x3d_particles_destroy": (I, [VP]),
+    "x3d_particles_prime": (I, [VP, VP, VP, VP, VP, c_int_p]),
+    "x3d_particles_advance": (I, [VP, VP, VP, VP, VP, c_int_p, ctypes.c_double]),
+    "x3d_particles_interpolate": (I, [VP, VP, VP, VP, VP, c_int_p, VP, I, VP]),
+    "x3d_particles_sort": (I, [VP, VP]),
+    "x3d_particles_pack": (I, [VP, VP, VP, ctypes.c_long]),
+    "x3d_particles_download": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, c_int_p]),
+    "x3d_particles_upload": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, I]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),
@@ -303,6 +312,12 @@ class LesParams(ctypes.Structure):
     """x3d_les_params of include/x3d2_hip.h"""
     _fields_ = [("model", I), ("c2", ctypes.c_double), ("a_x", VP), ("a_y", VP), ("a_z", VP), ("ih_x", VP), ("ih_y", VP),
                 ("ih_z", VP)]
+
+
+class ParticlesParams(ctypes.Structure):
+    """x3d_particles_params of include/x3d2_hip.h"""
+    _fields_ = [("n", I), ("order", I), ("wall", I), ("tau", ctypes.c_double), ("g", ctypes.c_double * 3), ("periodic", I * 3),
+                ("uniform", I * 3), ("L", ctypes.c_double * 3), ("coords", ctypes.POINTER(ctypes.c_double) * 3)]
 
 
 class BudgetFields(ctypes.Structure):

@@ -61,6 +61,9 @@ class BaseCase:
         self.loads = None
         # optional probes.Probes(solver, cfg, append=self.restarted): run() then samples, polls and finalises it
         self.probes = None
+        # optional particles.Particles(solver, cfg): run() then advances it at every step, writes, polls and finalises it (not in
+        # the reference)
+        self.particles = None
         self.restarted = False
         self.step_times = []
         self.initial_conditions()
@@ -196,8 +199,8 @@ class BaseCase:
             # a statistics, spectra or budgets sample, a row of the diagnostics series, a snapshot
             # (snapshot_manager.f90:125-126) and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step) read the
             # velocity like an output step does
-            loads, probes = self.loads, self.probes
-            attached = [a for a in (self.stats, self.spectra, diag, bud, probes, snap, ckpt) if a is not None]
+            loads, probes, parts = self.loads, self.probes, self.particles
+            attached = [a for a in (self.stats, self.spectra, diag, bud, probes, parts, snap, ckpt) if a is not None]
             read = (s.n_output > 0 and it % s.n_output == 0) or any(a.reads_state(it) for a in attached)
             snap_due = snap is not None and snap.reads_state(it)
             budgets_due = bud is not None and bud.pressure_due(it)  # (a budgets sample with pressure=True reads it too)
@@ -213,6 +216,8 @@ class BaseCase:
                 bud.update(it)  # nine gradients, the vertex pressure, one reduction, the recurrence; no host wait
             if probes is not None:
                 probes.update(it)  # one gather into the device table; no host wait
+            if parts is not None:
+                parts.update(it)  # one launch: advance, boundaries, sample (and the sort when it is due); no host wait
             if s.n_output > 0 and it % s.n_output == 0:
                 row = self.postprocess(it, it * s.dt)
                 if verbose and s.mesh.is_root():
@@ -227,6 +232,9 @@ class BaseCase:
             if snap is not None:
                 snap.write(it)  # packs and starts the copy; no host wait
                 snap.poll()     # files of the snapshots whose copies have landed
+            if parts is not None:
+                parts.write(it)  # packs and starts the copy; no host wait
+                parts.poll()
             if diag is not None:
                 diag.poll()     # rows of the tables whose copies have landed
             if loads is not None:
@@ -253,6 +261,8 @@ class BaseCase:
             self.loads.finalise()
         if self.probes is not None:
             self.probes.finalise()
+        if self.particles is not None:
+            self.particles.finalise()
         return self.monitoring.rows
 
 

@@ -14,7 +14,8 @@ The state, in this order: u, v, w; phi_<n> per species; for Adams-Bashforth of o
 variable in the integrator's list order (after its rotations); with active 3-D statistics their accumulators under
 Stats.state_dict's names (the profile mode's few KB go through state_dict on the host, and so do the running means of
 case.spectra under Spectra.state_dict's `spectra_*` names and the budget profiles of case.budgets under
-Budgets.state_dict's `budgets_*` names).
+Budgets.state_dict's `budgets_*` names, and the particles of case.particles under Particles.state_dict's `particles_*` names,
+in id order: 12 or 18 doubles and one int per particle).
 
 Scalars.  The reference's: timestep, time, dt, data_loc, ti_is_ab, ti_order, ti_istep, ti_nstep, stats_sample_count.
 Added here, because a resumed run must give the bits of the uninterrupted one:
@@ -119,6 +120,10 @@ class Checkpoints:
     def budgets(self):
         return getattr(self.case, "budgets", None) if self.case is not None else None
 
+    @property
+    def particles(self):
+        return getattr(self.case, "particles", None) if self.case is not None else None
+
     def _file_name(self, it, tag=""):
         m = self.solver.mesh
         return file_name(self.cfg.checkpoint_prefix, it, m.nproc, m.nrank, tag)
@@ -149,6 +154,9 @@ class Checkpoints:
         bud = self.budgets
         if bud is not None and bud.cfg.active:  # the running budget profiles: 41 x n doubles, through the host
             out.update(bud.state_dict())
+        parts = self.particles
+        if parts is not None:  # the particle state: through the host in id order (one host wait)
+            out.update(parts.state_dict())
         if self.case is not None:
             for k, v in self.case.checkpoint_state().items():
                 out["case_" + k] = np.asarray(v)
@@ -253,6 +261,7 @@ def restore(case, path):
     budgets = getattr(case, "budgets", None)
     if budgets is not None and not budgets.cfg.active:
         budgets = None
+    particles = getattr(case, "particles", None)
     # 2. does it fit?
     if int(z["precision"]) != REAL_BYTES:
         raise _differs("precision (bytes per real)", int(z["precision"]), REAL_BYTES)
@@ -299,6 +308,9 @@ def restore(case, path):
             raise X3dError("restore: this run samples budgets, the checkpoint holds none")
         # (raises on another profile_dir, another pressure setting or another length)
         moments_from_state(z, budgets.cfg.profile_dir, budgets.cfg.pressure, budgets.n_keep_global)
+    if particles is not None:
+        from .particles import check_state_dict
+        check_state_dict(z, particles.n, particles.cfg.order, particles.cfg.tau_p)  # (raises on none, another n, order, tau_p)
     # 3. upload, 4. the checksums of what arrived, one host wait
     n = int(np.prod(dims))
     data, off, total = b.checkpoint_layout(len(names), n)
@@ -334,6 +346,8 @@ def restore(case, path):
         spectra.load_state_dict(z)
     if budgets is not None:
         budgets.load_state_dict(z)
+    if particles is not None:
+        particles.load_state_dict(z)
     case.load_checkpoint_state({k[5:]: v for k, v in z.items() if k.startswith("case_")})
     case.restarted = True
     return s.current_iter

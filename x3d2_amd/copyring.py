@@ -9,7 +9,8 @@ landed waits for it, lands it, and counts `waits`.
 The copies of one backend share one in-order stream, so an older copy that is not done implies a newer one that is not:
 everything here goes oldest first.  The library keys its copy events by device pointer and has 16 per backend
 (X3D_SNAP_SLOTS): a slot is reallocated only when a larger size is asked for, and never while its copy is unlanded.  The
-rings of one backend together: Snapshots 2, Checkpoints 1, Diagnostics, Loads and Probes 2 each -- 9 with all attached."""
+rings of one backend together: Snapshots 2, Checkpoints 1, Diagnostics, Loads, Probes and Particles 2 each -- 11 with all
+attached."""
 from .common import X3dError
 
 

@@ -1,0 +1,354 @@
+"""Particles: Lagrangian tracers and inertial points, interpolated and advanced on the device (csrc/particles.hip).
+
+Not in the reference: this project's own addition.  A particle follows dx/dt = v with v = u(x) (tau_p = 0: a tracer) or
+dv/dt = (u(x) - v) / tau_p + g (an inertial point).  u(x) is a piecewise Lagrange interpolation of the vertex fields, per
+direction on the ACTUAL vertex coordinates (a stretched y needs nothing special):
+
+  wrap     periodic direction: x <- x - L floor(x / L); a result equal to L becomes 0
+  cell     i = the largest index with c[i] <= x; the last cell of a periodic direction runs to L, elsewhere i <= n - 2
+  nodes    order 2: i, i + 1.  order 4: s .. s + 3 with s = i - 1, clamped to [0, n - 4] in a non-periodic direction (one-sided
+           next to a wall), taken mod n in a periodic one, node m sitting at c[m mod n] + L floor(m / n)
+  weights  w_a = prod_{b != a} (x - xi_b) / (xi_a - xi_b)
+  value    sum_k w_k sum_j w_j sum_i w_i f[k][j][i]
+
+Time: second-order Adams-Bashforth on values stored with the particle (no old field is kept).  Construction primes the state
+from the fields as they are (a = u(x), v, F); update(it), called by BaseCase.run after step `it`, is ONE launch:
+
+  x += dt (c1 v + c0 v_prev)   [inertial: v += dt (c1 F + c0 F_prev)]     (c1, c0) = (1, 0) on the first advance, (1.5, -0.5) later
+  periodic directions wrap; a non-periodic one mirrors once about the wall it crossed ("reflect": an inertial v_d changes sign;
+  a particle still outside is clamped) or clamps and freezes the particle for good ("absorb": alive = 0)
+  a = u^it(x), tracers v = a, inertial F = (a - v) / tau_p + g; the history rotates
+
+so that x, v and a all belong to t_it afterwards.  A position that stops being finite freezes its particle (status 2) before
+any index is formed.  Particle state is FP64 in both flavours of the library.
+
+reads_state(it) is true at EVERY step from initpart - 1 on: a run with particles forgoes BaseCase.run's more=True deferral, as
+iprobefreq = 1 does.  Before initpart the particles rest; the state is primed again after step initpart - 1, which is why that
+step is completed like the ones that follow.
+
+sort_every = m > 0: after the updates with it % m == 0 the state is ordered by cell (a stable radix sort of the linear cell
+index and one gather of every array into a second set), so that neighbouring lanes gather from neighbouring cells.  Particles
+do not interact: a run's state by id has the same bits with any sort_every.
+
+Output: every ipartout steps one pack launch and one asynchronous copy through copyring.CopyRing (2 slots); poll() writes
+`<prefix>_<it:06d>.npz` (id, x[n, 3], v, a, alive, status, iteration, time, in id order) once the copy has landed; write never
+waits for the host.  state() is the same content now, with one host wait.
+
+One rank only."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .common import DIR_X, VERT, X3dError
+from .copyring import CopyRing
+from .diagnostics import global_vert_coords
+
+MAX_PARTICLES = 1 << 24  # X3D_PARTICLES_MAX of include/x3d2_hip.h
+WALLS = {"reflect": 0, "absorb": 1}
+DP = ctypes.POINTER(ctypes.c_double)
+ROWS = ("x", "v", "a", "v_prev", "F", "F_prev")  # three rows each; tracers hold the first four
+
+
+class ParticlesConfig:
+    """x0: [n, 3] start positions, 1 <= n <= 2^24; order 2 or 4; tau_p = 0: tracers; v0: [n, 3] start velocities of
+    inertial particles (None: the fluid's); wall: "reflect" or "absorb"; advance from iteration initpart on (<= 0: never);
+    a file every ipartout iterations (0: none); sort by cell every sort_every iterations (0: never; 8 is the measured
+    minimum of advance plus amortised sort, README)"""
+
+    def __init__(self, x0, order=4, tau_p=0.0, gravity=(0.0, 0.0, 0.0), v0=None, wall="reflect", initpart=1, ipartout=0,
+                 prefix="particles", sort_every=8):
+        x = np.array(x0, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != 3 or not 1 <= x.shape[0] <= MAX_PARTICLES:
+            raise X3dError("ParticlesConfig: x0 is an [n, 3] array of positions, 1 <= n <= %d" % MAX_PARTICLES)
+        if not np.all(np.isfinite(x)):
+            raise X3dError("ParticlesConfig: a position is not finite")
+        self.x0 = x
+        self.order = int(order)
+        if self.order not in (2, 4):
+            raise X3dError("ParticlesConfig: order is 2 or 4")
+        self.tau_p = float(tau_p)
+        if not np.isfinite(self.tau_p) or self.tau_p < 0.0:
+            raise X3dError("ParticlesConfig: tau_p must be finite and not negative")
+        g = np.array(gravity, dtype=np.float64)
+        if g.shape != (3,) or not np.all(np.isfinite(g)):
+            raise X3dError("ParticlesConfig: gravity is three finite values")
+        self.gravity = tuple(float(v) for v in g)
+        self.v0 = None
+        if v0 is not None:
+            if self.tau_p == 0.0:
+                raise X3dError("ParticlesConfig: v0 is for inertial particles (tau_p > 0); a tracer's velocity is the fluid's")
+            v = np.array(v0, dtype=np.float64)
+            if v.shape != x.shape or not np.all(np.isfinite(v)):
+                raise X3dError("ParticlesConfig: v0 is an [n, 3] array of finite velocities")
+            self.v0 = v
+        if wall not in WALLS:
+            raise X3dError("ParticlesConfig: wall is \"reflect\" or \"absorb\"")
+        self.wall = wall
+        self.initpart, self.ipartout, self.sort_every = int(initpart), int(ipartout), int(sort_every)
+        if self.ipartout < 0 or self.sort_every < 0:
+            raise X3dError("ParticlesConfig: ipartout and sort_every must not be negative")
+        self.prefix = str(prefix)
+
+    @property
+    def n(self):
+        return int(self.x0.shape[0])
+
+    @property
+    def inertial(self):
+        return self.tau_p > 0.0
+
+    def output_due(self, it):
+        return self.ipartout > 0 and it % self.ipartout == 0
+
+    def sort_due(self, it):
+        return self.sort_every > 0 and it % self.sort_every == 0
+
+
+def ab2_coefficients(first):
+    """(c1, c0) of x += dt (c1 v + c0 v_prev): explicit Euler on the first advance after priming, AB2 afterwards"""
+    return (1.0, 0.0) if first else (1.5, -0.5)
+
+
+def seed_uniform(mesh, n, seed=0):
+    """[n, 3] positions drawn uniformly over the domain: [0, L) of a periodic direction, [first, last vertex] of any other"""
+    rng = np.random.default_rng(seed)
+    out = np.empty((int(n), 3))
+    for d in range(3):
+        c = global_vert_coords(mesh, d)
+        lo, hi = (0.0, float(mesh.L[d])) if mesh.periodic_BC[d] else (float(c[0]), float(c[-1]))
+        out[:, d] = lo + (hi - lo) * rng.random(int(n))
+        if mesh.periodic_BC[d]:
+            out[:, d] = np.where(out[:, d] >= hi, 0.0, out[:, d])
+    return out
+
+
+def file_name(prefix, it):
+    return "%s_%06d.npz" % (prefix, int(it))
+
+
+def by_id(id_, *arrays):
+    """the arrays (particles along the LAST axis) brought from device order into id order"""
+    order = np.argsort(np.asarray(id_), kind="stable")
+    return [np.ascontiguousarray(np.asarray(a)[..., order]) for a in arrays]
+
+
+def unpack(raw, n):
+    """the bytes x3d_particles_pack wrote -> dict of id, x, v, a [n, 3], alive, status in id order"""
+    raw = np.asarray(raw)
+    rows = raw[:72 * n].view(np.float64).reshape(9, n)
+    ints = raw[72 * n:80 * n].view(np.int32).reshape(2, n)
+    rows, status = by_id(ints[0], rows, ints[1])
+    return {"id": np.arange(n, dtype=np.int64), "x": rows[0:3].T.copy(), "v": rows[3:6].T.copy(), "a": rows[6:9].T.copy(),
+            "alive": (status == 1).astype(np.int32), "status": status.astype(np.int32)}
+
+
+def load_particles(prefix, it):
+    """the file write(it) left, as a dict (id order): id, x, v, a, alive, status, iteration, time"""
+    name = file_name(prefix, it)
+    try:
+        with np.load(name, allow_pickle=False) as z:
+            out = {k: z[k] for k in z.files}
+    except Exception as e:
+        raise X3dError("load_particles: cannot read %s: %s: %s" % (name, type(e).__name__, e))
+    for k in ("id", "x", "v", "a", "alive", "iteration", "time"):
+        if k not in out:
+            raise X3dError("load_particles: %s is not a particle file: no `%s`" % (name, k))
+    return out
+
+
+def check_state_dict(z, n, order, tau_p):
+    """does the checkpoint `z` hold the particles of this run?  Raises an X3dError that names what differs."""
+    if "particles_n" not in z:
+        raise X3dError("restore: this run has particles, the checkpoint holds none")
+    for key, here in (("n", int(n)), ("order", int(order))):
+        if int(z["particles_" + key]) != here:
+            raise X3dError("restore: particles_%s differs: the checkpoint has %d, this run %d" % (key, int(z["particles_" + key]), here))
+    if float(z["particles_tau_p"]) != float(tau_p):
+        raise X3dError("restore: particles_tau_p differs: the checkpoint has %r, this run %r" % (float(z["particles_tau_p"]), float(tau_p)))
+    nrow = 18 if tau_p > 0.0 else 12
+    rows, status = np.asarray(z["particles_rows"]), np.asarray(z["particles_status"])
+    if rows.shape != (nrow, n) or rows.dtype != np.float64 or status.shape != (n,):
+        raise X3dError("restore: particles_rows is %s %s, this run needs float64 %s" % (rows.dtype.name, rows.shape, (nrow, n)))
+
+
+class Particles:
+    """Particles(solver, cfg), attached as `case.particles = Particles(case.solver, cfg)`: BaseCase.run then calls update(it),
+    write(it) and poll() once per step and finalise() at the end; checkpoint.Checkpoints carries state_dict()."""
+
+    def __init__(self, solver, cfg):
+        self.solver, self.cfg = solver, cfg
+        b, m = solver.backend, solver.mesh
+        if int(m.nproc) != 1:
+            raise X3dError("Particles: multi-rank particles are not built")
+        self.n, self.nrow = cfg.n, 18 if cfg.inertial else 12
+        dims = [int(v) for v in m.get_dims(VERT)]
+        if cfg.order == 4 and min(dims) < 4:
+            raise X3dError("Particles: order 4 needs at least 4 vertices per direction")
+        if cfg.inertial and cfg.tau_p < 2.0 * float(solver.dt):
+            raise X3dError("Particles: 0 < tau_p < 2 dt is refused (AB2 on the drag term needs dt / tau_p <= 0.5)")
+        self.coords = [np.ascontiguousarray(global_vert_coords(m, d), dtype=np.float64) for d in range(3)]
+        prm = _lib.ParticlesParams()
+        prm.n, prm.order, prm.wall, prm.tau = self.n, cfg.order, WALLS[cfg.wall], cfg.tau_p
+        for d in range(3):
+            prm.g[d] = cfg.gravity[d]
+            prm.periodic[d] = int(bool(m.periodic_BC[d]))
+            prm.uniform[d] = int(not m.stretched[d])
+            prm.L[d] = float(m.L[d])
+            prm.coords[d] = self.coords[d].ctypes.data_as(DP)
+        x0 = np.ascontiguousarray(cfg.x0.T)
+        v0 = np.ascontiguousarray(cfg.v0.T) if cfg.v0 is not None else None
+        self.lib, self.h = b.lib, ctypes.c_void_p()
+        _lib.check(b.lib.x3d_particles_create(b.h, ctypes.byref(prm), x0.ctypes.data_as(DP),
+                                              v0.ctypes.data_as(DP) if v0 is not None else None, ctypes.byref(self.h)))
+        self.ring = CopyRing(b, 2, self._write_file)  # (nothing is allocated until the first write)
+        self.files = []
+        self.iteration = int(solver.current_iter)  # the iteration the state belongs to
+        self.prime()
+
+    def __del__(self):
+        try:
+            if self.h is not None:
+                self.lib.x3d_particles_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------ the launches
+    def _fields(self, u, v, w):
+        b = self.solver.backend
+        for f in (u, v, w):
+            if f.dir != DIR_X:
+                raise X3dError("Particles: DIR_X fields are needed")
+        b._need_vert("Particles", u, v, w)
+        return u.ptr, v.ptr, w.ptr, b._dims(VERT)
+
+    def prime(self):
+        """a = u(x) from the solver's fields as they are; v and F from it.  The next advance is a first one."""
+        s = self.solver
+        s.flush_grad()  # a velocity correction left pending by step(more=True) is not in u, v, w yet
+        _lib.check(self.lib.x3d_particles_prime(s.backend.h, self.h, *self._fields(s.u, s.v, s.w)))
+
+    def advance(self, u, v, w, dt):
+        """one launch on fields of the caller's"""
+        _lib.check(self.lib.x3d_particles_advance(self.solver.backend.h, self.h, *self._fields(u, v, w), float(dt)))
+
+    def sort(self):
+        _lib.check(self.lib.x3d_particles_sort(self.solver.backend.h, self.h))
+
+    def interpolate(self, points, u, v, w):
+        """[m, 3] values of (u, v, w) at the [m, 3] points: one launch, one host wait.  A point outside a non-periodic
+        direction's [first, last vertex] or one that is not finite is an error."""
+        import torch
+        b = self.solver.backend
+        pts = np.array(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 3 or not 1 <= pts.shape[0] <= MAX_PARTICLES:
+            raise X3dError("Particles.interpolate: points is an [m, 3] array, 1 <= m <= %d" % MAX_PARTICLES)
+        if not np.all(np.isfinite(pts)):
+            raise X3dError("Particles.interpolate: a point is not finite")
+        for d in range(3):
+            c = self.coords[d]
+            if not self.solver.mesh.periodic_BC[d] and (np.any(pts[:, d] < c[0]) or np.any(pts[:, d] > c[-1])):
+                raise X3dError("Particles.interpolate: a point lies outside [%g, %g] of direction %d" % (c[0], c[-1], d + 1))
+        m = int(pts.shape[0])
+        ptrs = self._fields(u, v, w)
+        dev = torch.from_numpy(np.ascontiguousarray(pts.T)).to(b.device)
+        out = torch.empty((3, m), dtype=torch.float64, device=b.device)
+        _lib.check(self.lib.x3d_particles_interpolate(b.h, self.h, *ptrs, dev.data_ptr(), m, out.data_ptr()))
+        return out.cpu().numpy().T.copy()
+
+    # ------------------------------------------------------------ BaseCase.run's protocol
+    def reads_state(self, it):
+        """does update(it) read the solver's fields?  At every step from initpart on, and at initpart - 1, where the
+        resting particles are primed."""
+        return self.cfg.initpart > 0 and it >= self.cfg.initpart - 1
+
+    def update(self, it):
+        """advance to iteration `it` (the fields hold u^it, the state is at it - 1); returns whether the particles moved.
+        No host wait.  An iteration other than the next one is an error, never a silently skipped step."""
+        if it != self.iteration + 1:
+            raise X3dError("Particles.update: iteration %d after %d (every step is needed, in order)" % (it, self.iteration))
+        cfg, s = self.cfg, self.solver
+        moved = cfg.initpart > 0 and it >= cfg.initpart
+        if moved:
+            s.flush_grad()
+            self.advance(s.u, s.v, s.w, s.dt)
+            if cfg.sort_due(it):
+                self.sort()
+        elif self.reads_state(it):
+            self.prime()  # it == initpart - 1, resting until now: the history starts here
+        self.iteration = it  # (only once the launches were accepted: a refused advance leaves the count with the state)
+        return moved
+
+    def write(self, it):
+        """if iteration `it` is due: one pack launch, one asynchronous copy; no host wait unless both slots are in flight"""
+        if not self.cfg.output_due(it):
+            return False
+        if it != self.iteration:
+            raise X3dError("Particles.write: iteration %d, the state is at %d" % (it, self.iteration))
+        b = self.solver.backend
+        nbytes = 80 * self.n
+        slot = self.ring.acquire(nbytes)
+        _lib.check(self.lib.x3d_particles_pack(b.h, self.h, slot.dev.data_ptr(), nbytes))
+        self.ring.submit(slot, nbytes, (int(it), float(it * self.solver.dt)))
+        return True
+
+    def _write_file(self, payload, raw):
+        it, t = payload
+        out = unpack(raw, self.n)
+        out["iteration"], out["time"] = np.int64(it), np.float64(t)
+        name = file_name(self.cfg.prefix, it)
+        with open(name, "wb") as fh:
+            np.savez(fh, **out)
+        self.files.append(name)
+        return name
+
+    def poll(self):
+        """write the files whose copies have landed; never blocks"""
+        return self.ring.poll()
+
+    def finalise(self):
+        """wait for and write what is left"""
+        return self.ring.drain()
+
+    @property
+    def sync_count(self):
+        return self.ring.waits
+
+    # ------------------------------------------------------------ the state on the host
+    def raw_state(self):
+        """(rows [12 or 18, n], id, status, has_history) in DEVICE order; one host wait"""
+        rows = np.empty((self.nrow, self.n), dtype=np.float64)
+        id_, status = np.empty(self.n, dtype=np.int32), np.empty(self.n, dtype=np.int32)
+        hist = ctypes.c_int(0)
+        _lib.check(self.lib.x3d_particles_download(self.solver.backend.h, self.h, rows.ctypes.data_as(DP),
+                                                   id_.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p),
+                                                   ctypes.byref(hist)))
+        return rows, id_, status, bool(hist.value)
+
+    def state(self):
+        """id, x, v, a [n, 3], alive, status, iteration, time in id order: the only host wait"""
+        rows, id_, status, _ = self.raw_state()
+        rows, status = by_id(id_, rows, status)
+        return {"id": np.arange(self.n, dtype=np.int64), "x": rows[0:3].T.copy(), "v": rows[3:6].T.copy(),
+                "a": rows[6:9].T.copy(), "alive": (status == 1).astype(np.int32), "status": status.astype(np.int32),
+                "iteration": np.int64(self.iteration), "time": np.float64(self.iteration * self.solver.dt)}
+
+    def state_dict(self):
+        """everything a resumed run needs, through the host in id order, under `particles_*` keys: 12 (tracers) or 18
+        (inertial) doubles and one int per particle"""
+        rows, id_, status, hist = self.raw_state()
+        rows, status = by_id(id_, rows, status)
+        return {"particles_n": np.int64(self.n), "particles_order": np.int64(self.cfg.order),
+                "particles_tau_p": np.float64(self.cfg.tau_p), "particles_iteration": np.int64(self.iteration),
+                "particles_has_history": np.bool_(hist), "particles_rows": rows, "particles_status": status.astype(np.int32)}
+
+    def load_state_dict(self, z):
+        check_state_dict(z, self.n, self.cfg.order, self.cfg.tau_p)
+        rows = np.ascontiguousarray(z["particles_rows"], dtype=np.float64)
+        status = np.ascontiguousarray(z["particles_status"], dtype=np.int32)
+        id_ = np.arange(self.n, dtype=np.int32)
+        _lib.check(self.lib.x3d_particles_upload(self.solver.backend.h, self.h, rows.ctypes.data_as(DP),
+                                                 id_.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p),
+                                                 int(bool(z["particles_has_history"]))))
+        self.iteration = int(z["particles_iteration"])
