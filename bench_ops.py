@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles|scalars]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -80,6 +80,13 @@ of the default sort_every: 64 steps with 2^20 order-4 tracers at sort_every 0, 1
 (advance and the sorts that fall due), mean per step; (c) 20 fused RK3 steps with nothing attached, with Probes at every step
 (which gives up the more=True deferral as the particles do) and with 2^20 order-4 tracers (never sorted): wall time.  No gate.  The lines are
 appended to profiles/particles.jsonl.
+
+--family scalars (csrc/scalars.hip, x3d2_amd/scalars.py), at --snap-n (512) cubed, HIP events, the two sides of a comparison
+timed in turn inside one loop: (a) x3d_scalars_couple at ns = 1, up = y next to x3d_vecadd on the same blocks (both move three
+streams); gate t_couple <= 1.15 t_vecadd; (b) x3d_scalars_couple at ns = 3 with an oblique up and G != 0 next to the twelve
+x3d_vecadd calls that compose the same terms; (c) x3d_scalars_profile_sums at ns = 1 next to x3d_stats_profile_sums; (d) 20
+fused RK3 TGV steps with one passive species against the same run with ri = 1: what giving up the deferred branch costs (wall
+time).  The lines are appended to profiles/scalars.jsonl.
 """
 import argparse
 import json
@@ -1092,13 +1099,116 @@ def bench_particles(args):
               "ms_per_step_without": res["nothing"] / 20.0, "added_ms_per_step": (res[what] - res["nothing"]) / 20.0})
 
 
+def bench_scalars(args):
+    """one JSON line per measurement of the "scalars" family, printed and appended to profiles/scalars.jsonl"""
+    import ctypes
+
+    import torch
+    from x3d2_amd import _lib, make_tgv
+    from x3d2_amd.common import DIR_X, VERT
+    from x3d2_amd.scalars import Scalars, ScalarsConfig
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    out_path = os.path.join(ROOT, "profiles", "scalars.jsonl")
+
+    def emit(row):
+        row = dict({"family": "scalars", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    def alternating(fns):
+        """HIP-event ms of each fn in turn, --stat-iters rounds after --stat-warmup: both see the same machine state"""
+        ms, times = ctypes.c_float(), [[] for _ in fns]
+        for i in range(args.stat_warmup + args.stat_iters):
+            for k, fn in enumerate(fns):
+                _lib.check(b.lib.x3d_timer_start(b.h))
+                fn()
+                _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+                if i >= args.stat_warmup:
+                    times[k].append(ms.value)
+        return [spread(x) for x in times]
+
+    case = make_tgv(n, fused=True, n_species=3, pr_species=[1.0, 0.7, 2.0])
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    for i, f in enumerate(s.species):
+        f.set_data_loc(VERT)
+        b.veccopy(f, (s.u, s.v, s.u)[i])
+    d = [al.get_block(DIR_X, VERT) for _ in range(6)]
+    for f in d:
+        f.fill(0.0)
+    dof = float(n) ** 3
+    rate = lambda nbytes, t: {"bytes_per_dof": nbytes, "TBs": nbytes * dof / t["ms_median"] / 1e9,
+                              "ceiling": nbytes * dof / t["ms_median"] / 1e6 / 6200.0}
+    # (a) ns = 1, up = y: phi read, dv read and written -- what x3d_vecadd moves on the same blocks
+    one = lambda: b.scalars_couple(d[0:3], d[3:4], [s.u, s.v, s.w], s.species[0:1], (0, 1, 0), [1.0], [0.5])
+    t_c, t_v = alternating([one, lambda: b.vecadd(1.0, s.species[0], 1.0, d[1])])
+    emit(dict({"op": "x3d_scalars_couple, ns = 1, up = y (phi read, dv read and written)", "row_pitch": b.padded_dims[0]},
+              **rate(3 * rb, t_c), **t_c))
+    emit(dict({"op": "x3d_vecadd on the same blocks"}, **rate(3 * rb, t_v), **t_v))
+    limit = 1.15 * t_v["ms_median"]
+    emit({"op": "gate: t_couple(ns = 1) <= 1.15 t_vecadd", "couple_ms_median": t_c["ms_median"], "couple_ms_q1_q3": [t_c["ms_q1"], t_c["ms_q3"]],
+          "vecadd_ms_median": t_v["ms_median"], "vecadd_ms_q1_q3": [t_v["ms_q1"], t_v["ms_q3"]], "limit_ms": limit,
+          "ratio": t_c["ms_median"] / t_v["ms_median"], "passed": bool(t_c["ms_median"] <= limit)})
+    # (b) ns = 3, an oblique up, G != 0 on every species: 3 phi + 2 x 2 d + 3 vel + 2 x 3 dphi = 16 streams, next to the vecadd
+    # calls that compose the same terms (2 x 3 buoyancy + 6 advection: 12 calls of 3 streams)
+    up, ri, ref = (0.6, 0.8, 0.0), [1.0, 0.5, -0.25], [0.5, 0.0, 0.1]
+    grad = [(0.1, 0.2, 0.3), (0.0, 1.0, 0.0), (0.3, 0.0, -0.1)]
+    three = lambda: b.scalars_couple(d[0:3], d[3:6], [s.u, s.v, s.w], s.species, up, ri, ref, grad)
+
+    def composed():
+        for i in (0, 1):
+            for k in range(3):
+                b.vecadd(up[i] * ri[k], s.species[k], 1.0, d[i])  # (the reference values: one field_shift more per component)
+        for k in range(3):
+            for i, vel in enumerate((s.u, s.v, s.w)):
+                if grad[k][i] != 0.0:
+                    b.vecadd(-grad[k][i], vel, 1.0, d[3 + k])
+
+    t_c3, t_v3 = alternating([three, composed])
+    emit(dict({"op": "x3d_scalars_couple, ns = 3, up = (0.6, 0.8, 0), G != 0 (16 streams)"}, **rate(16 * rb, t_c3), **t_c3))
+    emit(dict({"op": "the 12 x3d_vecadd calls that compose the same terms (36 streams)"}, **rate(36 * rb, t_v3), **t_v3))
+    # (c) the plane sums, ns = 1, next to the statistics' on u, v, w
+    nk = n
+    z = lambda m: torch.zeros(m, dtype=_lib.torch_real(), device=b.device)
+    sums, mm, sums9 = z(5 * nk), z(2), z(9 * nk)
+    t_p, t_s = alternating([lambda: b.scalars_profile_sums(s.u, s.v, s.w, s.species[0:1], 2, sums, mm),
+                            lambda: b.stats_profile_sums(s.u, s.v, s.w, 2, sums9)])
+    emit(dict({"op": "x3d_scalars_profile_sums, ns = 1, dir_keep = 2 (u, v, w, phi read)"}, **rate(4 * rb, t_p), **t_p))
+    emit(dict({"op": "x3d_stats_profile_sums, dir_keep = 2 (u, v, w read)"}, **rate(3 * rb, t_s), **t_s))
+    for f in d:
+        al.release_block(f)
+    del case, s, b, al, d
+    torch.cuda.empty_cache()
+    # (d) 20 fused RK3 steps with one passive species against the same run with ri = 1: what giving up the deferred branch costs
+    res = {}
+    for ri1 in (0.0, 1.0):
+        case = make_tgv(n, fused=True, n_species=1)
+        s = case.solver
+        s.species[0].set_data_loc(VERT)
+        s.backend.veccopy(s.species[0], s.u)
+        s.scalars = Scalars(s, ScalarsConfig(ri=[ri1], up=(0, 0, 1)))
+        case.run(n_iters=3)
+        s.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        s.backend.sync()
+        res[ri1] = (time.perf_counter() - t0) * 1e3
+        del case, s
+        torch.cuda.empty_cache()
+    emit({"op": "TGV, fused, RK3, one species: 20 steps, ri = 0 (deferred branch) against ri = 1 (stored derivatives + coupling)",
+          "wall_ms_passive": res[0.0], "wall_ms_active": res[1.0], "ms_per_step_passive": res[0.0] / 20.0,
+          "added_ms_per_step": (res[1.0] - res[0.0]) / 20.0})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "loads",
-                                                               "budgets", "les", "particles"))
+                                                               "budgets", "les", "particles", "scalars"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -1123,7 +1233,9 @@ def main():
         bench_les(args)
     if args.family == "particles":
         bench_particles(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les", "particles"):
+    if args.family == "scalars":
+        bench_scalars(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les", "particles", "scalars"):
         return
     import torch
     from x3d2_amd import Mesh

@@ -1065,6 +1065,51 @@ int x3d_particles_pack(x3d_backend *b, const x3d_particles *p, void *dst_dev, lo
 int x3d_particles_download(x3d_backend *b, const x3d_particles *p, double *rows, int *id, int *status, int *has_history);
 int x3d_particles_upload(x3d_backend *b, x3d_particles *p, const double *rows, const int *id, const int *status, int has_history);
 
+/* ---- active scalars (csrc/scalars.hip).  Not in the reference: this project's own addition.  With ns species phi_s:
+ *    d_i      +=  up_i sum_s ri_s (phi_s - ref_s)                i = x, y, z     (Boussinesq buoyancy)
+ *    dphi_s   +=  -(G_s,x u + G_s,y v + G_s,z w)                                 (imposed mean scalar gradient)
+ * Every factor is converted to double before any product in BOTH flavours; each output is rounded once per launch.  Whole x
+ * rows per workgroup, 16-byte accesses along x with a scalar tail, long index arithmetic on the padded pitches; row padding is
+ * never read into a result and never written.  Up to X3D_SCALARS_GROUP species with something to do go in ONE launch.  More:
+ * the buoyancy of all of them in one launch of its own (a run-time loop over up to 64 species, so every momentum derivative is
+ * still rounded once; beyond 64, once per 64), then the imposed-gradient terms in groups of X3D_SCALARS_GROUP; the momentum
+ * part is complete after the last launch.  A launch touches only what its arguments require: d[i] is read and
+ * written only where up[i] != 0 and some ri != 0, vel only where some G != 0, dphi[s] only where G_s != 0, phi[s] only where
+ * ri[s] != 0; a species with ri = 0 and G = 0 is in no group, and nothing at all to do launches nothing.  No atomics.  Ordered
+ * on the backend's stream behind a queue of the deferred-execution layer, no host wait.  A bad argument (null, ns < 1, dims
+ * outside the block, a value that is not finite, an output that is an input or another output) is an error and launches
+ * nothing.  These entry points take blocks only: there is no handle that could belong to another backend. */
+#define X3D_SCALARS_GROUP 8
+typedef struct x3d_scalars_params {
+    int ns;             /* >= 1 */
+    double up[3];       /* the direction against gravity, not normalised: its length is part of the coefficient */
+    const double *ri;   /* host, ns values: Richardson-type coefficient per species (0: passive) */
+    const double *ref;  /* host, ns values: reference value per species */
+    const double *grad; /* host, [ns][3]: imposed mean gradient per species, or NULL: all zero */
+} x3d_scalars_params;
+int x3d_scalars_couple(x3d_backend *b, x3d_real *const d[3], x3d_real *const *dphi, const x3d_real *const vel[3],
+                       const x3d_real *const *phi, const int dims[3], const x3d_scalars_params *params);
+/* Dirichlet wall values: one launch per group of X3D_SCALARS_GROUP species stamps every requested face this rank owns.  Face
+ * 2 d + side (d = 0, 1, 2 for x, y, z; side 0 = first plane, 1 = last plane of dims) of species s is stamped with
+ * (x3d_real) value[6 s + 2 d + side] where bit 2 d + side of mask[s] & own_mask is set; own_mask says which faces of the
+ * global box lie in this rank's block (the caller decides it from the mesh offsets, as for the other face kernels).  A point
+ * shared by two stamped faces takes the value of the LATER direction in the order x, y, z (the thread of the earlier face
+ * skips it: no race).  Interior values and padding keep their bits.  Bad arguments as above; nothing to stamp launches
+ * nothing. */
+int x3d_scalars_apply_bc(x3d_backend *b, x3d_real *const *phi, int ns, const int dims[3], const int *mask, const double *value,
+                         int own_mask);
+/* One pass over u, v, w and the species.  sums[s][m][q] (device, ns * 5 * dims[dir_keep - 1] x3d_real) = the sums of
+ *    0 phi    1 phi phi    2 u phi    3 v phi    4 w phi
+ * over the unpadded extent dims of the two directions other than dir_keep (2 or 3; 1 is not built: an error) for every index q
+ * along it; minmax[s][2] (device, x3d_real) = min and max of phi_s over dims.  Factors are converted to double before any
+ * product, partials are double in both flavours, one rounding at the store.  Scheme and summation order as
+ * x3d_budget_profile_sums: per kept index and part, partial sums in a fixed order, added in part order by a second small
+ * launch; min / max through the same partials; no atomics; the launch geometry depends on dims, dir_keep and ns alone, so two
+ * samples of the same fields give the same bits.  The running mean is x3d_stats_profile_accumulate's. */
+#define X3D_SCALARS_NMOM 5
+int x3d_scalars_profile_sums(x3d_backend *b, const x3d_real *u, const x3d_real *v, const x3d_real *w, const x3d_real *const *phi,
+                             int ns, const int dims[3], int dir_keep, x3d_real *sums, x3d_real *minmax);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -27,7 +27,7 @@ def make_tgv(n, nproc_dir=(1, 1, 1), rank=0, Re=1600.0, dt=1e-3, time_intg="RK3"
 
 def make_channel(dims=(128, 65, 64), L=(4.0, 2.0, 2.0), stretching="top-bottom", beta=0.259065151, Re=4200.0,
                  dt=5e-3, time_intg="RK3", poisson="FFT", fused=False, device=None, comm=None, nproc_dir=(1, 1, 1),
-                 rank=0, lazy=None, lowmem_transeq=False, **channel_kw):
+                 rank=0, lazy=None, lowmem_transeq=False, n_species=0, pr_species=None, **channel_kw):
     """channel set-up of examples/channel/input.x3d: periodic x/z, no-slip y walls (Dirichlet),
     y stretched towards the walls; channel_kw -> ChannelConfig (rotation, omega_rot, n_rotate, noise).
     dims, L: the GLOBAL grid; nproc_dir = (1, 1, N): z slabs (the wall-normal direction stays whole on every rank:
@@ -40,8 +40,31 @@ def make_channel(dims=(128, 65, 64), L=(4.0, 2.0, 2.0), stretching="top-bottom",
                 st, (1.0, beta, 1.0), nrank=rank)
     backend = HipBackend(mesh, device=device, comm=comm, lazy=lazy)
     solver = Solver(backend, mesh, SolverConfig(Re=Re, dt=dt, time_intg=time_intg, poisson_solver_type=poisson,
-                                                 fused=fused, lowmem_transeq=lowmem_transeq))
+                                                 fused=fused, lowmem_transeq=lowmem_transeq, n_species=n_species,
+                                                 pr_species=pr_species))
     return ChannelCase(solver, ChannelConfig(**channel_kw))
+
+
+def make_rayleigh_benard(dims=(128, 65, 128), L=(4.0, 1.0, 4.0), Ra=1e6, Pr=1.0, stretching="uniform", beta=0.259065151,
+                         dt=2e-3, time_intg="RK3", poisson="FFT", fused=False, device=None, comm=None, nproc_dir=(1, 1, 1),
+                         rank=0, noise=1e-3, seed=None, **scalars_kw):
+    """Rayleigh-Benard convection on the channel's mesh and Poisson path (periodic x / z, no-slip y walls, z slabs allowed) in
+    free-fall units: Re = sqrt(Ra / Pr), one species (the temperature, pr_species = [Pr]) held at 1 below and 0 above, buoyancy
+    ri = 1 along up = (0, 1, 0), the fluid at rest on the conduction profile plus a seeded perturbation of amplitude `noise`
+    (case.RayleighBenardCase).  case.scalars is the attached scalars.Scalars with profile_dir = 2; scalars_kw -> its
+    ScalarsConfig (initstat, istatfreq, istatout, prefix).  Not in the reference."""
+    import math
+    from .backend import HipBackend
+    from .case import RayleighBenardCase, RayleighBenardConfig
+    from .solver import Solver, SolverConfig
+    if not (Ra > 0.0 and Pr > 0.0 and math.isfinite(Ra) and math.isfinite(Pr)):
+        raise X3dError("make_rayleigh_benard: Ra and Pr are positive and finite")
+    mesh = Mesh(tuple(dims), tuple(nproc_dir), tuple(L), ("periodic",) * 2, ("dirichlet",) * 2, ("periodic",) * 2,
+                ("uniform", stretching, "uniform"), (1.0, beta, 1.0), nrank=rank)
+    backend = HipBackend(mesh, device=device, comm=comm)
+    solver = Solver(backend, mesh, SolverConfig(Re=math.sqrt(Ra / Pr), dt=dt, time_intg=time_intg, poisson_solver_type=poisson,
+                                                 fused=fused, n_species=1, pr_species=[Pr]))
+    return RayleighBenardCase(solver, RayleighBenardConfig(noise=noise, seed=seed, **scalars_kw))
 
 
 def make_cylinder(dims=(257, 128, 32), L=(20.0, 12.0, 6.0), Re=300.0, dt=0.0075, time_intg="AB3", poisson="FFT",

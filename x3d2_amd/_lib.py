@@ -288,6 +288,9 @@ PROTOTYPES = {
     "x3d_particles_pack": (I, [VP, VP, VP, ctypes.c_long]),
     "x3d_particles_download": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, c_int_p]),
     "x3d_particles_upload": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, I]),
+    "x3d_scalars_couple": (I, [VP, ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), c_int_p, VP]),
+    "x3d_scalars_apply_bc": (I, [VP, ctypes.POINTER(VP), I, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_double), I]),
+    "x3d_scalars_profile_sums": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), I, c_int_p, I, VP, VP]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),
@@ -312,6 +315,12 @@ class LesParams(ctypes.Structure):
     """x3d_les_params of include/x3d2_hip.h"""
     _fields_ = [("model", I), ("c2", ctypes.c_double), ("a_x", VP), ("a_y", VP), ("a_z", VP), ("ih_x", VP), ("ih_y", VP),
                 ("ih_z", VP)]
+
+
+class ScalarsParams(ctypes.Structure):
+    """x3d_scalars_params of include/x3d2_hip.h"""
+    _fields_ = [("ns", I), ("up", ctypes.c_double * 3), ("ri", ctypes.POINTER(ctypes.c_double)),
+                ("ref", ctypes.POINTER(ctypes.c_double)), ("grad", ctypes.POINTER(ctypes.c_double))]
 
 
 class ParticlesParams(ctypes.Structure):

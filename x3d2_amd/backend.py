@@ -1249,6 +1249,48 @@ class HipBackend:
         self.red_epoch += 1  # (the partials live in the reduction buffer)
         _lib.check(self.lib.x3d_les_stress(self.h, p, _lib.ints(*dims), ctypes.byref(prm), VP(int(row_ptr))))
 
+    # ------------------------------------------------------------ active scalars (csrc/scalars.hip)
+    def scalars_couple(self, d, dphi, vel, phi, up, ri, ref, grad=None):
+        """d[i] += up[i] sum_s ri[s] (phi[s] - ref[s]);  dphi[s] -= grad[s] . vel -- all species in one launch per group of 8,
+        touching only what the arguments require (see include/x3d2_hip.h).  No host synchronisation."""
+        ns = len(phi)
+        if len(d) != 3 or len(vel) != 3 or len(dphi) != ns or len(ri) != ns or len(ref) != ns:
+            raise X3dError("scalars_couple: three momentum blocks, three velocities and one entry per species expected")
+        self._need_vert("scalars_couple", *vel, *phi)
+        dbl = ctypes.c_double
+        g = None if grad is None else (dbl * (3 * ns))(*[float(x) for row in grad for x in row])
+        prm = _lib.ScalarsParams(ns, (dbl * 3)(*[float(x) for x in up]), (dbl * max(ns, 1))(*[float(x) for x in ri]),
+                                 (dbl * max(ns, 1))(*[float(x) for x in ref]), g)
+        pp = lambda fs: (VP * max(len(fs), 1))(*[f.ptr for f in fs])
+        _lib.check(self.lib.x3d_scalars_couple(self.h, pp(d), pp(dphi), pp(vel), pp(phi), self._dims(VERT), ctypes.byref(prm)))
+
+    def scalars_apply_bc(self, phi, mask, value, own_mask):
+        """Dirichlet wall values of the species: face 2 d + side of phi[s] <- value[s][2 d + side] where bit 2 d + side of
+        mask[s] & own_mask is set; a point on two stamped faces takes the later direction's value (x, y, z)"""
+        ns = len(phi)
+        if len(mask) != ns or len(value) != ns:
+            raise X3dError("scalars_apply_bc: one mask and six values per species expected")
+        self._need_vert("scalars_apply_bc", *phi)
+        vals = (ctypes.c_double * (6 * max(ns, 1)))(*[float(x) for row in value for x in row])
+        _lib.check(self.lib.x3d_scalars_apply_bc(self.h, (VP * max(ns, 1))(*[f.ptr for f in phi]), ns, self._dims(VERT),
+                                                 _lib.ints(*mask) if ns else None, vals, int(own_mask)))
+
+    def scalars_profile_sums(self, u, v, w, phi, dir_keep, sums, minmax):
+        """sums (device tensor of ns * 5 * n_keep reals) <- the plane sums of phi, phi phi, u phi, v phi, w phi over this
+        rank's share of the two directions other than dir_keep (2 or 3); minmax (2 ns reals) <- min and max of every species
+        over this rank's interior.  Rank-local, no host synchronisation."""
+        ns = len(phi)
+        self._need_vert("scalars_profile_sums", u, v, w, *phi)
+        if dir_keep not in (DIR_Y, DIR_Z):
+            raise X3dError("scalars_profile_sums: dir_keep must be 2 or 3 (1 is not built)")
+        real = _lib.torch_real()
+        if sums.dtype != real or not sums.is_cuda or sums.numel() < 5 * ns * self.mesh.get_dims(VERT)[dir_keep - 1]:
+            raise X3dError("scalars_profile_sums: sums is a device tensor of ns * 5 * n_keep reals")
+        if minmax.dtype != real or not minmax.is_cuda or minmax.numel() < 2 * ns:
+            raise X3dError("scalars_profile_sums: minmax is a device tensor of 2 ns reals")
+        _lib.check(self.lib.x3d_scalars_profile_sums(self.h, u.ptr, v.ptr, w.ptr, (VP * max(ns, 1))(*[f.ptr for f in phi]), ns,
+                                                     self._dims(VERT), int(dir_keep), sums.data_ptr(), minmax.data_ptr()))
+
     # ------------------------------------------------------------ budget profiles (csrc/budget.hip)
     NBUDGET = 41  # X3D_NBUDGET of include/x3d2_hip.h
 

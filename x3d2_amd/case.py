@@ -132,7 +132,8 @@ class BaseCase:
             # cannot be formed inside the pressure correction's first kernels then -- the explicit order
             walls, defer_upd = None, False
         les = s.les
-        if s.fused and les is None and self.forcings_idle(it):
+        sca = s.scalars
+        if s.fused and les is None and self.forcings_idle(it) and (sca is None or not sca.coupled):
             # nothing touches the derivatives between transeq and the RK / AB stage: the last accumulation of
             # transeq may be folded into the stage's linear combination (Solver.transeq_fused)
             pending = s.transeq(deriv, curr, defer=True)
@@ -146,6 +147,9 @@ class BaseCase:
                 # the subgrid term reads the velocity transeq has completed (pending correction, bulk shift) and needs the
                 # derivatives stored: never the deferred branch above
                 les.add(deriv[0], deriv[1], deriv[2])
+            if sca is not None:
+                # buoyancy and the imposed-gradient term need the derivatives stored, like the subgrid term
+                sca.add(deriv, curr)
             if s.fused:
                 s.time_integrator.step(curr, deriv, s.dt, defer_update=defer_upd)
             else:
@@ -158,6 +162,8 @@ class BaseCase:
             s.pending_walls = walls  # apply_BC happens inside the pressure correction's first kernels
         else:
             self.apply_BC(s.u, s.v, s.w)
+        if sca is not None:
+            sca.apply_bc()  # (species are never part of a deferred update: the stage has written them)
         if ibm is not None:
             ibm.body(s.u, s.v, s.w)
         # not the last sub-step of the step and no hook looks at the velocity before the next transeq: its
@@ -199,8 +205,8 @@ class BaseCase:
             # a statistics, spectra or budgets sample, a row of the diagnostics series, a snapshot
             # (snapshot_manager.f90:125-126) and a checkpoint (checkpoint_manager.f90, handle_checkpoint_step) read the
             # velocity like an output step does
-            loads, probes, parts = self.loads, self.probes, self.particles
-            attached = [a for a in (self.stats, self.spectra, diag, bud, probes, parts, snap, ckpt) if a is not None]
+            loads, probes, parts, sca = self.loads, self.probes, self.particles, s.scalars
+            attached = [a for a in (self.stats, self.spectra, diag, bud, probes, parts, snap, ckpt, sca) if a is not None]
             read = (s.n_output > 0 and it % s.n_output == 0) or any(a.reads_state(it) for a in attached)
             snap_due = snap is not None and snap.reads_state(it)
             budgets_due = bud is not None and bud.pressure_due(it)  # (a budgets sample with pressure=True reads it too)
@@ -208,6 +214,8 @@ class BaseCase:
             s.current_iter = it
             if self.stats is not None:
                 self.stats.update(it)  # update_stats, base_case.f90:319
+            if sca is not None:
+                sca.update(it)  # one pass over u, v, w and the species, the recurrence; no host wait
             if self.spectra is not None:
                 self.spectra.update(it)  # the transforms and the reductions; no host wait
             if diag is not None:
@@ -225,6 +233,8 @@ class BaseCase:
                           % (row[0], it, row[1], row[2], row[3]))
             if self.stats is not None:
                 self.stats.write(it)  # handle_io_step, base_case.f90:328
+            if sca is not None:
+                sca.write(it)
             if self.spectra is not None:
                 self.spectra.write(it)
             if bud is not None:
@@ -400,6 +410,71 @@ class ChannelCase(BaseCase):
         return type(self).forcings is ChannelCase.forcings
 
     def apply_BC(self, u, v, w):  # :214-231
+        b = self.solver.backend
+        for f, st in zip((u, v, w), self.bc_start_y):
+            b.field_set_face_from_field(f, st, 0.0, Y_FACE)
+
+
+class RayleighBenardConfig:
+    """noise: amplitude of the seeded perturbation of the conduction profile; seed: of numpy's default_rng (None: drawn once
+    and carried by the checkpoints); scalars_kw -> ScalarsConfig (initstat, istatfreq, istatout, prefix)"""
+
+    def __init__(self, noise=1e-3, seed=None, **scalars_kw):
+        self.noise = float(noise)
+        self.seed = int(seed) if seed is not None else int(np.random.SeedSequence().entropy) & (2 ** 63 - 1)
+        self.scalars_kw = dict(scalars_kw)
+
+
+class RayleighBenardCase(BaseCase):
+    """Rayleigh-Benard convection between two no-slip walls in y, periodic in x and z; not in the reference.  Free-fall
+    units: the solver's Re is sqrt(Ra / Pr), its one species the temperature with pr_species = [Pr], held at 1 on the lower
+    and 0 on the upper wall, and buoyancy ri = 1 along up = (0, 1, 0) (scalars.Scalars, attached by this case as
+    solver.scalars with profile_dir = 2).  The fluid starts at rest on the conduction profile plus a seeded perturbation:
+        phi = 1 - y / H + noise sin(pi y / H) (2 r - 1),   r from default_rng(seed) on the GLOBAL grid, so that ranks agree
+    The velocity is held at zero on the walls the way the channel holds it (three zero wall fields, deferred_walls)."""
+
+    def __init__(self, solver, rb_cfg=None):
+        self.rb_cfg = rb_cfg or RayleighBenardConfig()
+        self.bc_start_y = None
+        super().__init__(solver)
+
+    @property
+    def scalars(self):
+        return self.solver.scalars
+
+    def initial_conditions(self):
+        from .scalars import Scalars, ScalarsConfig
+        s, m, c = self.solver, self.solver.mesh, self.rb_cfg
+        if s.nspecies != 1:
+            raise X3dError("RayleighBenardCase: the solver transports one species, the temperature")
+        for f in (s.u, s.v, s.w):
+            f.set_data_loc(VERT)
+            f.fill(0.0)
+        gx, gy, gz = (int(n) for n in m.get_global_dims(VERT))
+        nx, ny, nz = m.get_dims(VERT)
+        ox, oy, oz = (int(o) for o in m.n_offset)
+        H = float(m.L[1])
+        y = np.asarray(m.vert_coords[1])[None, :, None]
+        phi = (1.0 - y / H) * np.ones((nz, ny, nx))
+        if c.noise != 0.0:
+            r = np.random.default_rng(c.seed).random((gz, gy, gx))[oz:oz + nz, oy:oy + ny, ox:ox + nx]
+            phi = phi + c.noise * np.sin(np.pi * y / H) * (2.0 * r - 1.0)
+        self.bc_start_y = [s.backend.allocator.get_block(DIR_X, VERT) for _ in range(3)]
+        for f in self.bc_start_y:
+            f.fill(0.0)
+        s.scalars = Scalars(s, ScalarsConfig(ri=[1.0], ref=[0.0], up=(0, 1, 0), wall=[{"y": (1.0, 0.0)}], init=[phi],
+                                             profile_dir=2, **c.scalars_kw))
+
+    def checkpoint_state(self):
+        return {"seed": np.uint64(self.rb_cfg.seed)}
+
+    def load_checkpoint_state(self, state):
+        self.rb_cfg.seed = int(state["seed"])
+
+    def deferred_walls(self):
+        return self.bc_start_y
+
+    def apply_BC(self, u, v, w):
         b = self.solver.backend
         for f, st in zip((u, v, w), self.bc_start_y):
             b.field_set_face_from_field(f, st, 0.0, Y_FACE)

@@ -157,6 +157,9 @@ class Checkpoints:
         parts = self.particles
         if parts is not None:  # the particle state: through the host in id order (one host wait)
             out.update(parts.state_dict())
+        sca = getattr(s, "scalars", None)
+        if sca is not None and sca.profiling:  # the running scalar profiles: 5 x n values per species, through the host
+            out.update(sca.state_dict())
         if self.case is not None:
             for k, v in self.case.checkpoint_state().items():
                 out["case_" + k] = np.asarray(v)
@@ -262,6 +265,9 @@ def restore(case, path):
     if budgets is not None and not budgets.cfg.active:
         budgets = None
     particles = getattr(case, "particles", None)
+    scalars = getattr(s, "scalars", None)
+    if scalars is not None and not scalars.profiling:
+        scalars = None
     # 2. does it fit?
     if int(z["precision"]) != REAL_BYTES:
         raise _differs("precision (bytes per real)", int(z["precision"]), REAL_BYTES)
@@ -311,6 +317,8 @@ def restore(case, path):
     if particles is not None:
         from .particles import check_state_dict
         check_state_dict(z, particles.n, particles.cfg.order, particles.cfg.tau_p)  # (raises on none, another n, order, tau_p)
+    if scalars is not None:
+        scalars.check_state_dict(z)  # (raises on none, another profile_dir, another length or species count)
     # 3. upload, 4. the checksums of what arrived, one host wait
     n = int(np.prod(dims))
     data, off, total = b.checkpoint_layout(len(names), n)
@@ -348,6 +356,8 @@ def restore(case, path):
         budgets.load_state_dict(z)
     if particles is not None:
         particles.load_state_dict(z)
+    if scalars is not None:
+        scalars.load_state_dict(z)
     case.load_checkpoint_state({k[5:]: v for k, v in z.items() if k.startswith("case_")})
     case.restarted = True
     return s.current_iter
