@@ -375,6 +375,19 @@ int x3d_transeq_lincomb3(x3d_backend *b, int dir, x3d_real *du, x3d_real *dv, x3
                          const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym,
                          x3d_real *const y[3], const x3d_real *const base[3], const int nterm[3], const x3d_real *c,
                          x3d_real *const *x, const int ipend[3], const int store[3], int *done);
+/* ... with a second output per variable, the running sum of a Runge-Kutta step's final combination
+ * u = ((base + b_1 dt d_1) + b_2 dt d_2) + ...:  sout_i = sbase_i + sc[i] * d_i, rounded like a term of x3d_lincomb -- a
+ * partial sum of that chain stored here and continued by a later launch (or by x3d_lincomb) gives the bits of the chain
+ * in one go, and the derivatives need not be stored (store_i = 0).  sout[i] null: no second output for variable i.
+ * sout_i may be sbase_i (in place); sbase_i == base_i is read once for both outputs.  sout_i may alias nothing else the
+ * launch reads or writes (the fields, the derivative blocks, any y, base, term or other running sum): refused.
+ * Bit-identical to x3d_transeq_acc, then x3d_lincomb(y_i, ...), then x3d_lincomb(sout_i, sbase_i, 1, &sc[i], &dvar_i). */
+int x3d_transeq_lincomb3_sum(x3d_backend *b, int dir, x3d_real *du, x3d_real *dv, x3d_real *dw, const x3d_real *u,
+                             const x3d_real *v, const x3d_real *w, x3d_real nu, const x3d_tdsops *der1st,
+                             const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym,
+                             x3d_real *const y[3], const x3d_real *const base[3], const int nterm[3], const x3d_real *c,
+                             x3d_real *const *x, const int ipend[3], const int store[3], x3d_real *const sout[3],
+                             const x3d_real *const sbase[3], const x3d_real *sc, int *done);
 int x3d_lincomb_pending(x3d_backend *b, int dir, x3d_real *y, const x3d_real *base, int nterm, const x3d_real *c,
                         x3d_real *const *x, int ipend, const x3d_real *pend, int store);
 

@@ -652,10 +652,12 @@ class HipBackend:
         self.rk_fused_passes = getattr(self, "rk_fused_passes", 0) + n + 1
         self.rk_fused_launches = getattr(self, "rk_fused_launches", 0) + 1
 
-    def transeq_lincomb3(self, direction, rhs, vel, nu, dirps, specs):
+    def transeq_lincomb3(self, direction, rhs, vel, nu, dirps, specs, sums=None):
         """transeq_<direction> accumulated into rhs = (du, dv, dw) AND the stage's linear combination of every variable in
         the same launch (csrc/xscan.hip k_ytile_transeq3<EPI>): specs[i] = (y, base, coeffs, fields, store) with rhs[i] one of
-        `fields`.  False: these pencils are not served (nothing was done)"""
+        `fields`.  sums[i] = (sout, sbase, sc): the launch's second output sout = sbase + sc * d_i, the running sum of the
+        RK step's final combination (x3d_transeq_lincomb3_sum; sout may be sbase).  False: these pencils are not served
+        (nothing was done)"""
         y = (VP * 3)(*[sp[0].ptr for sp in specs])
         base = (VP * 3)(*[sp[1].ptr for sp in specs])
         nterm = _lib.ints(*[len(sp[3]) for sp in specs])
@@ -670,14 +672,26 @@ class HipBackend:
                 c[5 * i + k] = float(cv)
                 x[5 * i + k] = pv
         flag = ctypes.c_int(0)
-        _lib.check(self.lib.x3d_transeq_lincomb3(
-            self.h, direction, rhs[0].ptr, rhs[1].ptr, rhs[2].ptr, vel[0].ptr, vel[1].ptr, vel[2].ptr, float(nu),
-            dirps.der1st.handle, dirps.der1st_sym.handle, dirps.der2nd.handle, dirps.der2nd_sym.handle, y, base, nterm, c, x,
-            _lib.ints(*ipend), _lib.ints(*store), ctypes.byref(flag)))
+        args = [self.h, direction, rhs[0].ptr, rhs[1].ptr, rhs[2].ptr, vel[0].ptr, vel[1].ptr, vel[2].ptr, float(nu),
+                dirps.der1st.handle, dirps.der1st_sym.handle, dirps.der2nd.handle, dirps.der2nd_sym.handle, y, base, nterm, c, x,
+                _lib.ints(*ipend), _lib.ints(*store)]
+        if sums is None:
+            _lib.check(self.lib.x3d_transeq_lincomb3(*args, ctypes.byref(flag)))
+        else:
+            sout = (VP * 3)(*[sm[0].ptr for sm in sums])
+            sbase = (VP * 3)(*[sm[1].ptr for sm in sums])
+            sc = (_lib.REAL * 3)(*[float(sm[2]) for sm in sums])
+            _lib.check(self.lib.x3d_transeq_lincomb3_sum(*args, sout, sbase, sc, ctypes.byref(flag)))
         if flag.value:
-            self.rk_fused_passes = getattr(self, "rk_fused_passes", 0) + sum(len(sp[3]) + 1 for sp in specs)
+            # fields the stage reads or writes on top of the launch's own 64 B/DoF (which hold the store of d): base, the
+            # other terms and y; a running sum is its write -- in place of the store of d where that is not stored, so not
+            # counted again there -- and the read of sbase where that is not base
+            n = sum(len(sp[3]) + 1 for sp in specs)
+            for sp, sm in zip(specs, sums or ()):
+                n += (0 if not sp[4] else 1) + (1 if sm[1].ptr != sp[1].ptr else 0)
+            self.rk_fused_passes = getattr(self, "rk_fused_passes", 0) + n
             self.rk_fused_launches = getattr(self, "rk_fused_launches", 0) + 1
-            self.rk_in_tile3_passes = getattr(self, "rk_in_tile3_passes", 0) + sum(len(sp[3]) + 1 for sp in specs)
+            self.rk_in_tile3_passes = getattr(self, "rk_in_tile3_passes", 0) + n
             self.rk_in_tile3_launches = getattr(self, "rk_in_tile3_launches", 0) + 1
         return bool(flag.value)
 

@@ -211,12 +211,18 @@ int x3d_reduce_abs_partials_c(x3d_backend *b, const real_t *f, const int dims[3]
 #define X3D_BC_PARTS 1024
 // the RK / AB stage of one variable as the epilogue of a tile kernel (xscan.hip, k_ytile_transeq<EPI> / k_ytile_transeq3<EPI>):
 // d = x[ipend] + component;  [store: x[ipend] = d;]  y = base + sum_k c[k] (k == ipend ? d : x[k])
+// k_ytile_transeq3<EPI> only: sout != null adds a second output, the running sum of the stages' final combination,
+//     sout = sbase + sc * d
+// (sbase may be sout: in place; sbase null: it is base, whose rows then serve both outputs)
 struct TileEpi {
     real_t *y;
     const real_t *base;
     const real_t *x[5];
     real_t c[5];
     int n, ipend, store;
+    real_t *sout;
+    const real_t *sbase;
+    real_t sc;
 };
 #define X3D_NCU 256  // MI355X
 static inline int x3d_persistent_blocks(const x3d_backend *b, long want)

@@ -400,17 +400,20 @@ extern "C" int x3d_transeq_lincomb(x3d_backend *b, int dir, int kind, const real
 int x3d_ytile_transeq3_epi(x3d_backend *b, int dir, real_t *const r[3], const real_t *const f[3], real_t nu,
                            const x3d_tdsops *der1st, const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd,
                            const x3d_tdsops *der2nd_sym, const TileEpi epi[3], bool *done);
-extern "C" int x3d_transeq_lincomb3(x3d_backend *b, int dir, real_t *du, real_t *dv, real_t *dw, const real_t *u,
-                                    const real_t *v, const real_t *w, real_t nu, const x3d_tdsops *der1st,
-                                    const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym,
-                                    real_t *const y[3], const real_t *const base[3], const int nterm[3], const real_t *c,
-                                    real_t *const *x, const int ipend[3], const int store[3], int *done)
+// sout != null (x3d_transeq_lincomb3_sum): the launch's second output per variable, sout_i = sbase_i + sc[i] * d_i -- the
+// running sum of the final combination (TimeIntegrator.runge_kutta_fused); sout[i] null: none for that variable
+static int transeq_lincomb3_impl(x3d_backend *b, int dir, real_t *du, real_t *dv, real_t *dw, const real_t *u,
+                                 const real_t *v, const real_t *w, real_t nu, const x3d_tdsops *der1st,
+                                 const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym,
+                                 real_t *const y[3], const real_t *const base[3], const int nterm[3], const real_t *c,
+                                 real_t *const *x, const int ipend[3], const int store[3], real_t *const *sout,
+                                 const real_t *const *sbase, const real_t *sc, int *done)
 {
-    X3D_RANGE(__func__);
     if (b) X3D_LAZY_SYNC(b);
     X3D_LAZY_EAGER(b);
     X3D_REQUIRE(b && du && dv && dw && u && v && w && der1st && der1st_sym && der2nd && der2nd_sym && y && base && nterm &&
                 c && x && ipend && store && done, "x3d_transeq_lincomb3: null argument");
+    X3D_REQUIRE(!sout || (sbase && sc), "x3d_transeq_lincomb3_sum: null argument");
     X3D_REQUIRE(dir == X3D_DIR_Y || dir == X3D_DIR_Z, "x3d_transeq_lincomb3: dir must be y or z");
     *done = 0;
     real_t *dv_[3] = {du, dv, dw};
@@ -432,6 +435,20 @@ extern "C" int x3d_transeq_lincomb3(x3d_backend *b, int dir, real_t *du, real_t 
         r[cpt] = dv_[i];
         f[cpt] = fv[i];
         e[cpt].y = y[i]; e[cpt].base = base[i]; e[cpt].n = nterm[i]; e[cpt].ipend = ipend[i]; e[cpt].store = store[i];
+        e[cpt].sout = sout ? sout[i] : nullptr; e[cpt].sbase = nullptr; e[cpt].sc = 0.0;
+        if (e[cpt].sout) {
+            // (sout_i may BE sbase_i: a thread reads the rows it then writes; it may be nothing else the launch touches --
+            //  base_i and the terms are read after it is written, the fields and derivative blocks by other workgroups)
+            real_t *const so = e[cpt].sout;
+            X3D_REQUIRE(sbase[i], "x3d_transeq_lincomb3_sum: null argument");
+            bool clash = so == base[i];
+            for (int k = 0; k < 3; k++)
+                clash = clash || so == fv[k] || so == dv_[k] || so == y[k] || so == base[k] || (k != i && (so == sout[k] || so == sbase[k]));
+            for (int k = 0; k < 15; k++) clash = clash || (k / 5 < 3 && k % 5 < nterm[k / 5] && so == x[k]);
+            X3D_REQUIRE(!clash, "x3d_transeq_lincomb3_sum: a running sum aliases an input, a result or a derivative block of the launch");
+            e[cpt].sbase = sbase[i] == base[i] ? nullptr : sbase[i];  // (null: the rows of base_i, loaded once: xscan.hip)
+            e[cpt].sc = sc[i];
+        }
         for (int k = 0; k < 5; k++) {
             e[cpt].x[k] = k < nterm[i] ? x[5 * i + k] : x[5 * i];
             e[cpt].c[k] = k < nterm[i] ? c[5 * i + k] : 0.0;
@@ -441,4 +458,29 @@ extern "C" int x3d_transeq_lincomb3(x3d_backend *b, int dir, real_t *du, real_t 
     if (int rc = x3d_ytile_transeq3_epi(b, dir, r, f, nu, der1st, der1st_sym, der2nd, der2nd_sym, e, &ok)) return rc;
     *done = ok ? 1 : 0;
     return 0;
+}
+
+extern "C" int x3d_transeq_lincomb3(x3d_backend *b, int dir, real_t *du, real_t *dv, real_t *dw, const real_t *u,
+                                    const real_t *v, const real_t *w, real_t nu, const x3d_tdsops *der1st,
+                                    const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd, const x3d_tdsops *der2nd_sym,
+                                    real_t *const y[3], const real_t *const base[3], const int nterm[3], const real_t *c,
+                                    real_t *const *x, const int ipend[3], const int store[3], int *done)
+{
+    X3D_RANGE(__func__);
+    return transeq_lincomb3_impl(b, dir, du, dv, dw, u, v, w, nu, der1st, der1st_sym, der2nd, der2nd_sym, y, base, nterm, c, x,
+                                 ipend, store, nullptr, nullptr, nullptr, done);
+}
+
+extern "C" int x3d_transeq_lincomb3_sum(x3d_backend *b, int dir, real_t *du, real_t *dv, real_t *dw, const real_t *u,
+                                        const real_t *v, const real_t *w, real_t nu, const x3d_tdsops *der1st,
+                                        const x3d_tdsops *der1st_sym, const x3d_tdsops *der2nd,
+                                        const x3d_tdsops *der2nd_sym, real_t *const y[3], const real_t *const base[3],
+                                        const int nterm[3], const real_t *c, real_t *const *x, const int ipend[3],
+                                        const int store[3], real_t *const sout[3], const real_t *const sbase[3],
+                                        const real_t sc[3], int *done)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(sout && sbase && sc, "x3d_transeq_lincomb3_sum: null argument");
+    return transeq_lincomb3_impl(b, dir, du, dv, dw, u, v, w, nu, der1st, der1st_sym, der2nd, der2nd_sym, y, base, nterm, c, x,
+                                 ipend, store, sout, sbase, sc, done);
 }

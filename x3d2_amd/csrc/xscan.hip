@@ -991,6 +991,8 @@ __device__ __forceinline__ const real2_t *tile_row(const real_t *base, long prow
 // read back by the stage's kernel (and without writing it after the last stage).  epp: three TileEpi in device memory,
 // component order (advecting component first).  Per step the EPI launches save 6 of ~ 200 field passes (stages 1 and 3
 // of RK3; stage 2 gains nothing: DESIGN.md 3.2) and trade the stage kernel's streaming rate for the tile pattern's.
+// With epi.sout the store phase has a second output, sout_c = sbase_c + sc * d: the running sum of an RK step's final
+// combination, written where d would be (x3d_transeq_lincomb3_sum: 3 more passes per RK3 step go away).
 // NPW (round 6): pencils per wave.  2 = a tile of 32 x-adjacent pencils, wave w solves pencils w and w + 16 one after the
 // other.  FP32: a row of the tile is then a 128-byte segment again (16 pencils of 4-byte reals are 64 bytes) and the
 // workgroup holds as many bytes in flight as a 512-row FP64 tile, at the same register counts (NI and the advecting rows
@@ -1241,6 +1243,25 @@ __global__ void __launch_bounds__(1024)
                         d[i].y += old[i].y;
                         if (epi.store) *const_cast<real2_t *>(tile_row<RP>(o, prow, i, voff)) = d[i];
                     }
+                    // the second output, the running sum sout = sc * d + sbase (the shape of a term below: k_lincomb's bits).
+                    // sbase null: base's rows, which bs holds, serve both outputs.  Otherwise its rows are requested behind
+                    // the store of y, where bs is dead: ahead of the term loop they are 16 more live VGPRs (the 512-row
+                    // instantiations then spill 84).  The description is read where it is used, through the laundered
+                    // pointer again, and the host tells the two cases apart: comparing sbase with base here keeps two
+                    // more SGPR pairs alive behind the barrier, and the 512-row circulant form spills 12 VGPRs for it.
+                    // In place (sbase == sout) a thread reads the rows it then writes
+                    {
+                        const TileEpi *ps = epp + c;
+                        asm volatile("" : "+s"(ps) : "v"(d[0].x));
+                        real_t *const sout = ps->sout;
+                        if (sout != nullptr && ps->sbase == nullptr) {
+                            const real_t sc = ps->sc;
+#pragma unroll
+                            for (int i = 0; i < NI; i++)
+                                *const_cast<real2_t *>(tile_row<RP>(sout + off, prow, i, voff)) =
+                                    make_real2(sc * d[i].x + bs[i].x, sc * d[i].y + bs[i].y);
+                        }
+                    }
 #pragma unroll  // (static indices into epi: a run-time index would put the struct on the stack)
                     for (int k = 0; k < 5; k++) {
                         if (k >= epi.n) continue;
@@ -1256,6 +1277,20 @@ __global__ void __launch_bounds__(1024)
                     }
 #pragma unroll
                     for (int i = 0; i < NI; i++) *const_cast<real2_t *>(tile_row<RP>(epi.y + off, prow, i, voff)) = bs[i];
+                    {
+                        const TileEpi *ps = epp + c;
+                        asm volatile("" : "+s"(ps) : "v"(bs[0].x));
+                        real_t *const sout = ps->sout;
+                        const real_t *const sbase = ps->sbase;
+                        if (sout != nullptr && sbase != nullptr) {
+                            const real_t sc = ps->sc;
+                            gload(bs, sbase + off);
+#pragma unroll
+                            for (int i = 0; i < NI; i++)
+                                *const_cast<real2_t *>(tile_row<RP>(sout + off, prow, i, voff)) =
+                                    make_real2(sc * d[i].x + bs[i].x, sc * d[i].y + bs[i].y);
+                        }
+                    }
                 } else {
                 __syncthreads();
 #pragma unroll
@@ -1867,6 +1902,7 @@ int x3d_ytile_transeq_lincomb(x3d_backend *b, int dir, real_t *rhs, const real_t
 {
     TileEpi e;
     e.y = y; e.base = base; e.n = nterm; e.ipend = ipend; e.store = store;
+    e.sout = nullptr; e.sbase = nullptr; e.sc = 0.0;  // (the second output: the three-component launch only)
     for (int k = 0; k < 5; k++) { e.x[k] = k < nterm ? x[k] : x[0]; e.c[k] = k < nterm ? c[k] : 0.0; }
     return ytile_transeq_impl(b, dir, rhs, u, conv, nu, t1, t2, t3, 1, &e, done);
 }

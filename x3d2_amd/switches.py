@@ -25,6 +25,7 @@ TABLE = (
     ("X3D_NO_ROT_FUSED", "flag", False, "rotation and mean shift as separate launches"),
     ("X3D_NO_DEFER", "flag", False, "no deferred accumulation of the transeq terms into the stage's linear combination"),
     ("X3D_NO_EPI3", "flag", False, "the stage not as the epilogue of the three-in-one z launch"),
+    ("X3D_NO_RK_RUNSUM", "flag", False, "RK stages in the z launch store the derivatives, not the running sum of the final combination"),
     ("X3D_STAGE_IN_TILE", "flag", False, "the stage in the per-component z tile kernel"),
     ("X3D_NO_DEFER_GRAD", "flag", False, "pressure gradient applied at once, not folded into the next x launch"),
     ("X3D_NO_DEFER_WALLS", "flag", False, "channel: wall values set by separate launches"),

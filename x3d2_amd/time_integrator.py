@@ -20,6 +20,7 @@ class TimeIntegrator:
     def __init__(self, backend, allocator, method, nvars=3, fused=False):
         self.backend, self.allocator, self.sname = backend, allocator, method
         self.defer_update, self.pending_update = False, {}
+        self._runsum = self._e_written = False  # runge_kutta_fused: this step carries the running sum (see _runsum_stage)
         self.fused = fused
         self.gdt = 0.0
         try:
@@ -148,6 +149,11 @@ class TimeIntegrator:
         # round 5: transeq's z launch is still pending for u, v, w and will do their stage itself (Solver.transeq_fused,
         # HipBackend.transeq_lincomb3): (direction, nu, dirps); the fields are the ones this stage's swaps leave in place
         tile3 = pending.pop("tile3", None) if pending else None
+        if self.istage == 1:
+            self._runsum = False  # decided below for the whole step
+        if self._runsum or (self.istage == 1 and tile3 is not None and self._runsum_wanted()):
+            if self._runsum_stage(curr, deriv, dt, pending, tile3):
+                return
         in_transeq = False
         if self.istage == ns:
             specs = []
@@ -191,6 +197,75 @@ class TimeIntegrator:
                     b.veccopy(sp[0], sp[1])
             self._flush(pending)
             self.istage += 1
+
+    # ---- the running sum (stages in the z launch).  The final combination u = ((base + b_1 dt d_1) + b_2 dt d_2) + ... is
+    # evaluated left to right by k_lincomb and by the launch's term loop, so a partial sum of it stored as a field and
+    # continued by the next stage gives the bits of the chain in one go.  Where the launch does the stage it writes d
+    # explicitly; writing e_s = e_{s-1} + b_s dt d_s instead (e_0 = base; HipBackend.transeq_lincomb3, sums) leaves the last
+    # stage with base = e and ONE term, three reads per variable fewer than base + every stored derivative (RK3, RK4).
+    # e lives in olds[i][1]; the derivative blocks are not swapped into olds on such a step.
+    def _runsum_wanted(self):
+        """stage 1: this step may carry the running sum -- every earlier stage's row of RK_A has its diagonal entry alone
+        (y_s = base + a_ss dt d_s needs no stored derivative) and X3D_NO_RK_RUNSUM is not set"""
+        ns, a = self.nstage, self.RK_A[self.nstage]
+        if ns < 2 or getattr(getattr(self.backend, "sw", None), "no_rk_runsum", True):
+            return False
+        return all(a[s][s] != 0.0 and not any(a[s][j] != 0.0 for j in range(3) if j != s) for s in range(ns - 1))
+
+    def _runsum_stage(self, curr, deriv, dt, pending, tile3):
+        """one stage of a step in the running-sum form.  Stage 1 returns False with nothing done when the z launch does not
+        take it in this form: the step then runs in the stored-derivative form.  A later stage the z launch does not do
+        continues from e with the plain calls, which give the same bits"""
+        b, ns, st = self.backend, self.nstage, self.istage
+        a, bb = self.RK_A[ns], self.RK_B[ns]
+        last = st == ns
+        if st == 1:
+            for i in range(3):
+                self._swap(self.olds[i][0], curr[i])  # olds1 <- curr (curr is rewritten below)
+            self._e_written = False                   # (no b_k != 0 yet: e is still the base itself, nothing stored)
+        base = [self.olds[i][0] for i in range(3)]
+        e = [self.olds[i][1] for i in range(3)]
+        esrc = e if self._e_written else base
+        bc = bb[st - 1] * dt
+        if last:
+            specs = [(curr[i], esrc[i], [bc], [deriv[i]], False) for i in range(3)]
+            sums = None
+        else:
+            specs = [(curr[i], base[i], [a[st - 1][st - 1] * dt], [deriv[i]], False) for i in range(3)]
+            sums = [(e[i], esrc[i], bc) for i in range(3)] if bb[st - 1] != 0.0 else None
+        vel = base if st == 1 else curr[:3]
+        rhs = deriv[:3]
+        if tile3 is not None and b.transeq_lincomb3(tile3[0], rhs, vel, tile3[1], tile3[2], specs, sums):
+            self.n_stage_in_transeq = getattr(self, "n_stage_in_transeq", 0) + 1
+        elif st == 1:
+            for i in range(3):
+                self._swap(self.olds[i][0], curr[i])
+            return False
+        else:
+            if tile3 is not None:
+                self._complete_transeq(tile3, rhs, vel)
+            for i, sp in enumerate(specs):
+                self._lincomb(sp[0], sp[1], sp[2], sp[3], pending, not last, var=i)
+                if sums:
+                    b.lincomb(sums[i][0], sums[i][1], [bc], [deriv[i]])
+        if sums:
+            self._e_written = True
+        self._runsum = not last
+        # every variable beyond the first three: the stored-derivative form
+        for i in range(3, self.nvars):
+            if last:
+                terms = [(bb[j - 1] * dt, self.olds[i][j]) for j in range(1, ns) if bb[j - 1] != 0.0]
+                terms.append((bc, deriv[i]))
+                self._lincomb(curr[i], self.olds[i][0], [c for c, _ in terms], [f for _, f in terms], pending, False, var=i)
+            else:
+                if st == 1:
+                    self._swap(self.olds[i][0], curr[i])
+                self._swap(self.olds[i][st], deriv[i])
+                terms = [(a[st - 1][j - 1] * dt, self.olds[i][j]) for j in range(1, st + 1) if a[st - 1][j - 1] != 0.0]
+                self._lincomb(curr[i], self.olds[i][0], [c for c, _ in terms], [f for _, f in terms], pending, True, var=i)
+        self._flush(pending)
+        self.istage = 1 if last else st + 1
+        return True
 
     def _complete_transeq(self, tile3, rhs, vel):
         """the pending z launch as a plain accumulating transeq (the stage then runs as usual); returns False"""
