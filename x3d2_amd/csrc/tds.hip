@@ -1008,12 +1008,18 @@ extern "C" int x3d_tds_solve_acc(x3d_backend *b, real_t *du, const real_t *u, co
                                  int accumulate, real_t scale)
 {
     X3D_RANGE(__func__);
-    if (b) X3D_LAZY_SYNC(b);
-    X3D_LAZY_EAGER(b);
     X3D_REQUIRE(b && du && u && t, "x3d_tds_solve: null argument");
     X3D_REQUIRE(x3d_dir_ok(dir), "x3d_tds_solve: bad dir %d", dir);
     X3D_REQUIRE(du != u, "x3d_tds_solve: du and u must be distinct blocks");
     if (int rc = check_len(b, t, dir, "tds_solve")) return rc;
+    // deferred execution: what has been recorded runs first, then the solve works at once on the buffers that hold the two
+    // handles' data.  (Restoring the identity map here, X3D_LAZY_SYNC, cost a run whose add-ons form velocity gradients or the
+    // vertex pressure -- Les.add, Snapshots, Diagnostics, Budgets -- 35 to 47 block copies in two steps at 32^3:
+    // tests/test_hip_lazy_addons.py.)  Inside a queued operation or another entry point that runs at once the pointers are
+    // buffers already and stay as they are.
+    X3D_LAZY_IN(b, u);
+    X3D_LAZY_OUT(b, du, !accumulate);
+    X3D_LAZY_EAGER(b);
     if (dir == X3D_DIR_X) return x3d_xdir_tds(b, du, u, t, accumulate, scale);
     // default on: single-pass solve for periodic 512-row y/z pencils, 0.50 ms vs 0.85 ms for the
     // two-sweep pair (profiles/README.md); X3D_NO_ONCHIP2=1 falls back
