@@ -69,7 +69,10 @@ both launches (HIP events), for both models, in TB/s on the 128 B/DoF it reads a
 restored before every timed call: the kernel works in place), next to the fused statistics update (168 B/DoF, also a read +
 write stream) in the same process, and the gate t_stress <= 1.25 (128 / 168) t_stats_update; (b) a whole Les.add next to a
 whole Diagnostics sample, wall clock around a device sync; (c) 20 fused RK3 TGV steps with and without the model: added wall
-time per step (no gate).  The lines are appended to profiles/les.jsonl.
+time per step (no gate); (d) x3d_les_scalar_flux (the species' subgrid flux; 56 B/DoF for one species, 104 B/DoF for two in
+FP64) with the fused statistics update timed in the same loop, and the gates t_flux <= 1.25 (56 / 168) t_stats_update and
+1.25 (104 / 168); (e) a whole Les.add with one species; (f) 20 fused RK3 TGV steps with LES alone, with one species alone and
+with both (no gate).  The lines are appended to profiles/les.jsonl.
 
 Family "particles" (--snap-n^3 = 512^3, median of --stat-iters with the quartiles as spread; not part of "all"), on the velocity
 of a fused TGV run three steps old: (a) x3d_particles_advance (HIP events) for 2^16, 2^20 and 2^22 particles, orders 2 and 4,
@@ -1000,6 +1003,99 @@ def bench_les(args):
     for model in ("smagorinsky", "wale"):
         emit({"op": "TGV, fused, RK3: 20 steps, %s" % model, "wall_ms_without": res[None], "wall_ms_with": res[model],
               "ms_per_step_without": res[None] / 20.0, "added_ms_per_step": (res[model] - res[None]) / 20.0})
+    # (d) the species' subgrid flux: x3d_les_scalar_flux for one and two species next to the fused statistics update in the
+    # same loop; the kernel works in place, so the six gradients are copied back (untimed) before every timed call
+    from x3d2_amd.common import DIR_Y, DIR_Z
+    from x3d2_amd.les import NUT_BLOCK, PHI_BLOCK
+    case = make_tgv(n, fused=True, n_species=1, pr_species=[0.7])
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    s.species[0].set_data_loc(VERT)
+    b.veccopy(s.species[0], s.u)  # (a field with gradients: the case leaves its species unset)
+    case.step(1)
+    s.flush_grad()
+    les = Les(s, LesConfig(model="wale", prt=0.85))
+    grads = s.velocity_gradients()
+    les.stress(grads)
+    dirs = ((s.xdirps, DIR_X), (s.ydirps, DIR_Y), (s.zdirps, DIR_Z))
+    gb = [grads[m] for m in PHI_BLOCK]
+    for q, f in enumerate((s.species[0], s.v)):
+        for j, (dirps, direction) in enumerate(dirs):
+            b.tds_apply(gb[3 * q + j], f, dirps.der1st, direction)
+    saved = [al.get_block(DIR_X, VERT) for _ in range(6)]
+    for d, g in zip(saved, gb):
+        b.veccopy(d, g)
+    acc = [al.get_block(DIR_X, VERT) for _ in range(9)]
+    for f in acc:
+        f.fill(0.0)
+    row = torch.zeros(2, dtype=torch.float64, device=b.device)
+    ms, times = ctypes.c_float(), {1: [], 2: [], "stats": []}
+    for i in range(args.stat_warmup + args.stat_iters):
+        for ns in (1, 2):
+            for d, g in zip(saved, gb):
+                b.veccopy(g, d)
+            _lib.check(b.lib.x3d_timer_start(b.h))
+            b.les_scalar_flux(grads[NUT_BLOCK], gb[:3 * ns], [1.0 / 0.85, 1.0 / 0.4][:ns], row.data_ptr())
+            _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times[ns].append(ms.value)
+        _lib.check(b.lib.x3d_timer_start(b.h))
+        b.stats_update_uvw(s.u, s.v, s.w, acc, 0.125)
+        _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+        if i >= args.stat_warmup:
+            times["stats"].append(ms.value)
+    t_stats = spread(times["stats"])
+    nbytes = 21 * rb * n ** 3
+    emit(dict({"op": "x3d_stats_update_uvw in the loop of x3d_les_scalar_flux (3 blocks read, 9 read and written)",
+               "bytes_per_dof": 21 * rb, "TBs": nbytes / t_stats["ms_median"] / 1e9,
+               "ceiling": nbytes / t_stats["ms_median"] / 1e6 / 6200.0}, **t_stats))
+    for ns in (1, 2):
+        t = spread(times[ns])
+        dof = (1 + 6 * ns) * rb
+        nbytes = dof * n ** 3
+        emit(dict({"op": "x3d_les_scalar_flux, ns = %d: both launches (%d blocks read, %d written)" % (ns, 1 + 3 * ns, 3 * ns),
+                   "bytes_per_dof": dof, "TBs": nbytes / t["ms_median"] / 1e9, "ceiling": nbytes / t["ms_median"] / 1e6 / 6200.0,
+                   "row_pitch": b.padded_dims[0]}, **t))
+        limit = 1.25 * (dof / (21.0 * rb)) * t_stats["ms_median"]
+        emit({"op": "gate: t_flux <= 1.25 (%d / %d) t_stats_update, ns = %d" % (dof, 21 * rb, ns), "flux_ms_median": t["ms_median"],
+              "stats_update_ms_median": t_stats["ms_median"], "limit_ms": limit, "ratio_to_limit": t["ms_median"] / limit,
+              "passed": bool(t["ms_median"] <= limit)})
+    for f in grads + saved + acc:
+        al.release_block(f)
+    # (e) a whole Les.add with one species, from call to return (wall clock around a device sync)
+    d = [al.get_block(DIR_X, VERT) for _ in range(4)]
+    for f in d:
+        f.fill(0.0)
+    s0 = b.sync_count()
+    t = spread(timed_wall(args, b, lambda: les.add(d[0], d[1], d[2], [d[3]], list(s.species))))
+    emit(dict({"op": "Les.add, wale, one species: 9 + 3 gradients, stress, flux, 9 + 3 accumulated derivatives (wall clock)",
+               "stream_syncs_per_call": (b.sync_count() - s0) / float(args.stat_warmup + args.stat_iters),
+               "monitor": les.monitor()}, **t))
+    del case, s, b, al, les, grads, gb, saved, acc, d
+    torch.cuda.empty_cache()
+    # (f) 20 steps: LES without species, one species without LES, LES with one species (the first two are the parent's paths)
+    setups = (("LES (wale) without species", 0, LesConfig(model="wale")), ("one species without LES", 1, None),
+              ("LES (wale, prt = 0.85) with one species", 1, LesConfig(model="wale", prt=0.85)))
+    res = {}
+    for name, nspec, cfg in setups:
+        case = make_tgv(n, fused=True, **(dict(n_species=1, pr_species=[0.7]) if nspec else {}))
+        if nspec:
+            case.solver.species[0].set_data_loc(VERT)
+            case.solver.backend.veccopy(case.solver.species[0], case.solver.u)
+        if cfg is not None:
+            case.solver.les = Les(case.solver, cfg)
+        case.run(n_iters=3)
+        case.solver.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        case.solver.backend.sync()
+        res[name] = (time.perf_counter() - t0) * 1e3
+        emit({"op": "TGV, fused, RK3: 20 steps, " + name, "wall_ms": res[name], "ms_per_step": res[name] / 20.0})
+        del case
+        torch.cuda.empty_cache()
+    a, c, both = (res[name] for name, _, _ in setups)
+    emit({"op": "TGV, fused, RK3: 20 steps: what a species adds to an LES step, and the model to a step with a species",
+          "added_ms_per_step_species_to_les": (both - a) / 20.0, "added_ms_per_step_les_to_species": (both - c) / 20.0})
 
 
 def bench_particles(args):

@@ -1009,6 +1009,19 @@ typedef struct x3d_les_params {
     const double *ih_x, *ih_y, *ih_z; /* device tables of inverse spacings, as x3d_diag_params' */
 } x3d_les_params;
 int x3d_les_stress(x3d_backend *b, x3d_real *const grads[9], const int dims[3], const x3d_les_params *params, double *row_dev);
+/* The subgrid scalar flux of ns = 1 or 2 transported species from the nu_t block x3d_les_stress leaves in grads[3] (read
+ * once for both species) and the species' gradient blocks gphi[3 s + j] = d phi_s / d x_j, j = x, y, z, which are overwritten
+ * in place.  Per point, every factor widened to double before any product, in BOTH flavours:
+ *    kappa = nu_t inv_prt[s]      q_j = kappa gphi[3 s + j], each rounded once to x3d_real, -> gphi[3 s + j]
+ *    row_dev[s] = sum over the dims interior of kappa ((g_x^2 + g_y^2) + g_z^2)      (ns doubles in both flavours)
+ * inv_prt[ns] is a HOST array of 1 / Pr_t (the eddy diffusivity is nu_t / Pr_t), row_dev[ns] a device array.  Work mapping,
+ * tail handling, the deterministic two-launch sum in the backend's reduction buffer and the ordering rules are
+ * x3d_les_stress's: row padding is neither read into a result nor written, no atomics, two calls on the same blocks give the
+ * same bits, no host wait, a queue of the deferred-execution layer runs first.  A bad argument (a null pointer, ns outside
+ * 1..2, non-positive dims or dims outside the block, an inv_prt that is not finite and positive, nut equal to one of gphi,
+ * two equal gphi, more partials than the reduction buffer holds) is an error and launches nothing.  Not in the reference. */
+int x3d_les_scalar_flux(x3d_backend *b, const x3d_real *nut, x3d_real *const gphi[], int ns, const int dims[3],
+                        const double *inv_prt, double *row_dev);
 
 /* ---- point probes (csrc/probe.hip).  Not in the reference: this project's own addition.  A probe sits on a vertex; a sample
  * is the value of u, v, w there, widened to double, in row_dev[3 slot + c] of a row of 3 n_total doubles. */

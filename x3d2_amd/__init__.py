@@ -47,12 +47,15 @@ def make_channel(dims=(128, 65, 64), L=(4.0, 2.0, 2.0), stretching="top-bottom",
 
 def make_rayleigh_benard(dims=(128, 65, 128), L=(4.0, 1.0, 4.0), Ra=1e6, Pr=1.0, stretching="uniform", beta=0.259065151,
                          dt=2e-3, time_intg="RK3", poisson="FFT", fused=False, device=None, comm=None, nproc_dir=(1, 1, 1),
-                         rank=0, noise=1e-3, seed=None, **scalars_kw):
+                         rank=0, noise=1e-3, seed=None, les=None, **scalars_kw):
     """Rayleigh-Benard convection on the channel's mesh and Poisson path (periodic x / z, no-slip y walls, z slabs allowed) in
     free-fall units: Re = sqrt(Ra / Pr), one species (the temperature, pr_species = [Pr]) held at 1 below and 0 above, buoyancy
     ri = 1 along up = (0, 1, 0), the fluid at rest on the conduction profile plus a seeded perturbation of amplitude `noise`
     (case.RayleighBenardCase).  case.scalars is the attached scalars.Scalars with profile_dir = 2; scalars_kw -> its
-    ScalarsConfig (initstat, istatfreq, istatout, prefix).  Not in the reference."""
+    ScalarsConfig (initstat, istatfreq, istatout, prefix).  les: a les.LesConfig, or None (no model) -- les.Les is attached
+    as solver.les before the scalars, with the eddy diffusivity nu_t / Pr_t for the temperature; a config without prt gets
+    prt = 0.85, which is this project's choice (a common value for air-like fluids), not the reference's.  Not in the
+    reference."""
     import math
     from .backend import HipBackend
     from .case import RayleighBenardCase, RayleighBenardConfig
@@ -64,6 +67,13 @@ def make_rayleigh_benard(dims=(128, 65, 128), L=(4.0, 1.0, 4.0), Ra=1e6, Pr=1.0,
     backend = HipBackend(mesh, device=device, comm=comm)
     solver = Solver(backend, mesh, SolverConfig(Re=math.sqrt(Ra / Pr), dt=dt, time_intg=time_intg, poisson_solver_type=poisson,
                                                  fused=fused, n_species=1, pr_species=[Pr]))
+    if les is not None:
+        from .les import Les, LesConfig
+        if not isinstance(les, LesConfig):
+            raise X3dError("make_rayleigh_benard: les is a LesConfig or None")
+        if les.prt is None:
+            les = LesConfig(model=les.model, cs=les.cs, cw=les.cw, prt=0.85)
+        solver.les = Les(solver, les)  # (before the case attaches Scalars, which asks the model whether it serves species)
     return RayleighBenardCase(solver, RayleighBenardConfig(noise=noise, seed=seed, **scalars_kw))
 
 

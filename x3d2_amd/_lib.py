@@ -279,6 +279,7 @@ PROTOTYPES = {
     "x3d_budget_profile_sums": (I, [VP, VP, c_int_p, I, ctypes.c_double, VP]),
     "x3d_budget_profile_accumulate": (I, [VP, VP, VP, ctypes.c_long, ctypes.c_double, ctypes.c_double]),
     "x3d_les_stress": (I, [VP, ctypes.POINTER(VP), c_int_p, VP, VP]),
+    "x3d_les_scalar_flux": (I, [VP, VP, ctypes.POINTER(VP), I, c_int_p, ctypes.POINTER(ctypes.c_double), VP]),
     "x3d_probe_create": (I, [VP, c_int_p, I, c_int_p, I, ctypes.POINTER(VP)]),
     "x3d_probe_sample": (I, [VP, VP, VP, VP, VP, c_int_p, VP]),
     "x3d_probe_destroy": (I, [VP]),

@@ -9,6 +9,7 @@ happens in libx3d2_hip.so through the C ABI (include/x3d2_hip.h); this class
 only sequences calls and does the neighbour exchanges.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -1262,6 +1263,25 @@ class HipBackend:
         p = (VP * 9)(*[g.ptr for g in grads])
         self.red_epoch += 1  # (the partials live in the reduction buffer)
         _lib.check(self.lib.x3d_les_stress(self.h, p, _lib.ints(*dims), ctypes.byref(prm), VP(int(row_ptr))))
+
+    def les_scalar_flux(self, nut, gphi, inv_prt, row_ptr):
+        """the subgrid scalar flux of one or two species, in place: gphi = their gradient fields (x, y, z of the first, then
+        of the second) <- nut * inv_prt[s] * gradient, and sum nut inv_prt[s] |grad phi_s|^2 -> the doubles at the device
+        address row_ptr, one per species; nut = the eddy-viscosity field les_stress leaves in grads[3]; inv_prt = 1 / Pr_t
+        per species, host numbers.  No host synchronisation."""
+        ns = len(inv_prt)
+        if ns not in (1, 2):
+            raise X3dError("les_scalar_flux: one or two species per call")
+        if len(gphi) != 3 * ns:
+            raise X3dError("les_scalar_flux: three gradient fields per species expected")
+        ipr = [float(x) for x in inv_prt]
+        if not all(math.isfinite(x) and x > 0.0 for x in ipr):
+            raise X3dError("les_scalar_flux: 1 / Pr_t must be finite and positive")
+        self._need_vert("les_scalar_flux", nut, *gphi)
+        p = (VP * (3 * ns))(*[g.ptr for g in gphi])
+        self.red_epoch += 1  # (the partials live in the reduction buffer)
+        _lib.check(self.lib.x3d_les_scalar_flux(self.h, nut.ptr, p, ns, self._dims(VERT), (ctypes.c_double * ns)(*ipr),
+                                                VP(int(row_ptr))))
 
     # ------------------------------------------------------------ active scalars (csrc/scalars.hip)
     def scalars_couple(self, d, dphi, vel, phi, up, ri, ref, grad=None):

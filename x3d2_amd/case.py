@@ -146,7 +146,10 @@ class BaseCase:
             if les is not None:
                 # the subgrid term reads the velocity transeq has completed (pending correction, bulk shift) and needs the
                 # derivatives stored: never the deferred branch above
-                les.add(deriv[0], deriv[1], deriv[2])
+                if getattr(les, "serves_species", False):  # (eddy diffusivity: the species' subgrid flux with it)
+                    les.add(deriv[0], deriv[1], deriv[2], deriv[3:], curr[3:])
+                else:
+                    les.add(deriv[0], deriv[1], deriv[2])
             if sca is not None:
                 # buoyancy and the imposed-gradient term need the derivatives stored, like the subgrid term
                 sca.add(deriv, curr)

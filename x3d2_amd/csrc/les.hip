@@ -20,6 +20,11 @@
 // thread, 256 threads side by side along x in one (j, k) row; item t = row * nchunk + chunk goes to workgroup t mod G,
 // G = min(items, 512).  A thread adds its items in the order it meets them, a wave adds its lanes by the shuffle tree
 // 32, 16, .. 1, the four waves are added in wave order, the G partials in index order by a second small launch.  No atomics.
+//
+// Species (x3d_les_scalar_flux, at the end of this file): the eddy diffusivity kappa = nu_t / Pr_t and the flux q_j = kappa
+// dphi/dx_j of one or two species, in place on their gradient blocks, from the nu_t block the stress kernel leaves behind, and
+// sum kappa |grad phi|^2 per species.  It takes the stress kernel's item map, loads and partial sums (les_place, les_ld_blocks,
+// les_sum_partials), which left k_les_stress's machine code as it was.
 #include "common.h"
 
 #define LES_NSLOT 4
@@ -42,29 +47,54 @@ struct LesItem {
     int n;  // points of this vector inside the row: <= 0 none, >= LES_V all
 };
 
-// the vector of item t that belongs to this thread; points beyond nx read as zero gradients on a zero width
-__device__ __forceinline__ void les_load(const LesArgs &A, long t, LesItem &it)
+// where item t = row * nchunk + chunk puts this thread: the offset of its vector in a block, the points of it inside the row
+// (<= 0 none, >= LES_V all) and its indices.  Shared by the stress and the scalar-flux kernels.
+struct LesPlace {
+    long off, k;
+    int n, i0, j;
+};
+__device__ __forceinline__ LesPlace les_place(int nx, int ny, int nchunk, long nxp, long nyp, long t)
 {
-    const long row = t / A.nchunk;
-    const int ch = (int)(t - row * A.nchunk);
-    const int j = (int)(row % A.ny);
-    const long k = row / A.ny;
-    const int i0 = (ch * 256 + (int)threadIdx.x) * LES_V;
-    it.off = A.nxp * (j + A.nyp * k) + i0;  // (nxp is a multiple of 16 elements: 16-byte aligned)
-    it.n = A.nx - i0;
-    if (it.n >= LES_V) {
+    LesPlace p;
+    const long row = t / nchunk;
+    const int ch = (int)(t - row * nchunk);
+    p.j = (int)(row % ny);
+    p.k = row / ny;
+    p.i0 = (ch * 256 + (int)threadIdx.x) * LES_V;
+    p.off = nxp * (p.j + nyp * p.k) + p.i0;  // (nxp is a multiple of 16 elements: 16-byte aligned)
+    p.n = nx - p.i0;
+    return p;
+}
+
+// the vectors of NB blocks at one place, non-temporal: one 16-byte load per block, or point by point in the row's tail;
+// points beyond the row read as zero and the row padding is not touched
+template <int NB>
+__device__ __forceinline__ void les_ld_blocks(real_t *const (&f)[NB], long off, int n, real_t (&g)[NB][LES_V])
+{
+    if (n >= LES_V) {
 #pragma unroll
-        for (int m = 0; m < 9; m++) {
-            const les_vec x = __builtin_nontemporal_load(reinterpret_cast<const les_vec *>(A.f[m] + it.off));
+        for (int m = 0; m < NB; m++) {
+            const les_vec x = __builtin_nontemporal_load(reinterpret_cast<const les_vec *>(f[m] + off));
 #pragma unroll
-            for (int q = 0; q < LES_V; q++) it.g[m][q] = x[q];
+            for (int q = 0; q < LES_V; q++) g[m][q] = x[q];
         }
     } else {
 #pragma unroll
-        for (int m = 0; m < 9; m++)
+        for (int m = 0; m < NB; m++)
 #pragma unroll
-            for (int q = 0; q < LES_V; q++) it.g[m][q] = q < it.n ? __builtin_nontemporal_load(A.f[m] + it.off + q) : (real_t)0;
+            for (int q = 0; q < LES_V; q++) g[m][q] = q < n ? __builtin_nontemporal_load(f[m] + off + q) : (real_t)0;
     }
+}
+
+// the vector of item t that belongs to this thread; points beyond nx read as zero gradients on a zero width
+__device__ __forceinline__ void les_load(const LesArgs &A, long t, LesItem &it)
+{
+    const LesPlace p = les_place(A.nx, A.ny, A.nchunk, A.nxp, A.nyp, t);
+    const int j = p.j, i0 = p.i0;
+    const long k = p.k;
+    it.off = p.off;
+    it.n = p.n;
+    les_ld_blocks<9>(A.f, it.off, it.n, it.g);
     const double ay = A.a_y[j], az = A.a_z[k], hy = A.ih_y[j], hz = A.ih_z[k];
     const double hyz = hy * hy + hz * hz;
 #pragma unroll
@@ -181,6 +211,23 @@ __global__ void __launch_bounds__(256) k_les_stress(LesArgs A, double *part)
     }
 }
 
+// partials part[p * STRIDE + slot], p < nparts, added in index order with a compensated sum: one fixed order, the same bits for
+// the same partials
+template <int STRIDE>
+__device__ __forceinline__ double les_sum_partials(const double *__restrict__ part, int nparts, int slot)
+{
+    double r = 0.0, c = 0.0;
+#pragma unroll 4
+    for (int p = 0; p < nparts; p++) {
+        const double x = part[(long)p * STRIDE + slot];
+        const double t = r + x;
+        c += fabs(r) >= fabs(x) ? (r - t) + x : (x - t) + r;
+        r = t;
+    }
+    r += c;
+    return r;
+}
+
 // stage 2: the partials in index order (the sums compensated, as k_diag_finish's: one fixed order, the same bits for the
 // same partials)
 __global__ void __launch_bounds__(64) k_les_finish(const double *__restrict__ part, int nparts, double *__restrict__ row)
@@ -189,15 +236,7 @@ __global__ void __launch_bounds__(64) k_les_finish(const double *__restrict__ pa
     if (slot >= LES_NSLOT) return;
     double r = 0.0;
     if (slot < 2) {
-        double c = 0.0;
-#pragma unroll 4
-        for (int p = 0; p < nparts; p++) {
-            const double x = part[(long)p * LES_NSLOT + slot];
-            const double t = r + x;
-            c += fabs(r) >= fabs(x) ? (r - t) + x : (x - t) + r;
-            r = t;
-        }
-        r += c;
+        r = les_sum_partials<LES_NSLOT>(part, nparts, slot);
     } else {
 #pragma unroll 8
         for (int p = 0; p < nparts; p++) r = fmax(r, part[(long)p * LES_NSLOT + slot]);
@@ -263,6 +302,181 @@ extern "C" int x3d_les_stress(x3d_backend *b, x3d_real *const grads[9], const in
     else
         hipLaunchKernelGGL(k_les_stress<1>, dim3(grid), dim3(256), 0, b->stream, A, part);
     hipLaunchKernelGGL(k_les_finish, dim3(1), dim3(64), 0, b->stream, (const double *)part, grid, row_dev);
+    X3D_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the species' subgrid flux: eddy diffusivity kappa = nu_t / Pr_t and q_j = kappa dphi/dx_j, in place on the gradient blocks
+// of one or two species, from the nu_t block x3d_les_stress leaves behind (read once for both species).  Per point and
+// species, every factor widened to double before any product, in both flavours:
+//    kappa = nu_t inv_prt[s];   q_j = kappa g_j, each rounded once to the real kind;   row[s] += kappa ((g_x^2 + g_y^2) + g_z^2)
+// Mapping, tail handling and summation order are k_les_stress's (above): the same work items on the same workgroups, the
+// next item's loads issued before the current item's stores, the shuffle tree, the four waves in wave order, the partials in
+// the backend's reduction buffer added in index order by a second small launch.  No atomics: two launches on the same
+// blocks give the same bits.  1 + 3 ns blocks read and 3 ns written: 56 B per point (ns = 1) and 104 B (ns = 2) in FP64.
+template <int NS>
+struct LesFluxArgs {
+    real_t *f[1 + 3 * NS];  // nu_t (only read), then g_x, g_y, g_z of each species (overwritten by q_x, q_y, q_z)
+    double ipr[NS];         // 1 / Pr_t of each species
+    int nx, ny, nchunk;
+    long nitem, nxp, nyp;
+};
+
+template <int NS>
+struct LesFluxItem {
+    real_t g[1 + 3 * NS][LES_V];
+    long off;
+    int n;
+};
+
+template <int NS>
+__device__ __forceinline__ void les_flux_load(const LesFluxArgs<NS> &A, long t, LesFluxItem<NS> &it)
+{
+    const LesPlace p = les_place(A.nx, A.ny, A.nchunk, A.nxp, A.nyp, t);
+    it.off = p.off;
+    it.n = p.n;
+    les_ld_blocks<1 + 3 * NS>(A.f, it.off, it.n, it.g);
+}
+
+// the fluxes of the item's points into it.g[1 ..], kappa |grad phi|^2 into s (points beyond the row hold zeros and add zero)
+template <int NS>
+__device__ __forceinline__ void les_flux_point(const LesFluxArgs<NS> &A, LesFluxItem<NS> &it, double (&s)[NS])
+{
+#pragma unroll
+    for (int q = 0; q < LES_V; q++) {
+        const double nut = it.g[0][q];
+#pragma unroll
+        for (int sp = 0; sp < NS; sp++) {
+            const double kap = nut * A.ipr[sp];
+            const double gx = it.g[1 + 3 * sp][q], gy = it.g[2 + 3 * sp][q], gz = it.g[3 + 3 * sp][q];
+            s[sp] += kap * ((gx * gx + gy * gy) + gz * gz);
+            it.g[1 + 3 * sp][q] = (real_t)(kap * gx);
+            it.g[2 + 3 * sp][q] = (real_t)(kap * gy);
+            it.g[3 + 3 * sp][q] = (real_t)(kap * gz);
+        }
+    }
+}
+
+template <int NS>
+__device__ __forceinline__ void les_flux_store(const LesFluxArgs<NS> &A, const LesFluxItem<NS> &it)
+{
+    if (it.n >= LES_V) {
+#pragma unroll
+        for (int m = 1; m < 1 + 3 * NS; m++) {
+            les_vec x;
+#pragma unroll
+            for (int q = 0; q < LES_V; q++) x[q] = it.g[m][q];
+            *reinterpret_cast<les_vec *>(A.f[m] + it.off) = x;
+        }
+    } else {
+#pragma unroll
+        for (int m = 1; m < 1 + 3 * NS; m++)
+#pragma unroll
+            for (int q = 0; q < LES_V; q++)
+                if (q < it.n) A.f[m][it.off + q] = it.g[m][q];
+    }
+}
+
+// stage 1: the fluxes in place and part[workgroup][NS]
+template <int NS>
+__global__ void __launch_bounds__(256) k_les_scalar_flux(LesFluxArgs<NS> A, double *part)
+{
+    __shared__ double sm[4][NS];
+    double s[NS];
+#pragma unroll
+    for (int m = 0; m < NS; m++) s[m] = 0.0;
+    const long G = gridDim.x;
+    long t = blockIdx.x;  // (G <= nitem: every workgroup has a first item)
+    LesFluxItem<NS> cur;
+    les_flux_load<NS>(A, t, cur);
+    for (t += G; t < A.nitem; t += G) {
+        LesFluxItem<NS> nxt;
+        les_flux_load<NS>(A, t, nxt);
+        les_flux_point<NS>(A, cur, s);
+        les_flux_store<NS>(A, cur);
+        cur = nxt;
+    }
+    les_flux_point<NS>(A, cur, s);
+    les_flux_store<NS>(A, cur);
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int m = 0; m < NS; m++) s[m] += __shfl_down(s[m], o);
+    }
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    if (ln == 0) {
+#pragma unroll
+        for (int m = 0; m < NS; m++) sm[wv][m] = s[m];
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        const int slot = threadIdx.x;
+        part[(long)blockIdx.x * NS + slot] = ((sm[0][slot] + sm[1][slot]) + sm[2][slot]) + sm[3][slot];
+    }
+}
+
+// stage 2: row[s] = the partials of species s in index order, compensated as k_les_finish's sums
+template <int NS>
+__global__ void __launch_bounds__(64) k_les_flux_finish(const double *__restrict__ part, int nparts, double *__restrict__ row)
+{
+    const int slot = threadIdx.x;
+    if (slot >= NS) return;
+    row[slot] = les_sum_partials<NS>(part, nparts, slot);
+}
+
+template <int NS>
+static void les_flux_launch(x3d_backend *b, const real_t *nut, real_t *const g[], const double *inv_prt, const int dims[3],
+                            int grid, double *row_dev)
+{
+    LesFluxArgs<NS> A;
+    A.f[0] = const_cast<real_t *>(nut);
+    for (int m = 0; m < 3 * NS; m++) A.f[1 + m] = g[m];
+    for (int s = 0; s < NS; s++) A.ipr[s] = inv_prt[s];
+    A.nx = dims[0];
+    A.ny = dims[1];
+    A.nchunk = (dims[0] + 256 * LES_V - 1) / (256 * LES_V);
+    A.nitem = (long)dims[1] * dims[2] * A.nchunk;
+    A.nxp = b->nxp;
+    A.nyp = b->nyp;
+    double *part = reinterpret_cast<double *>(b->red_buf);
+    hipLaunchKernelGGL(k_les_scalar_flux<NS>, dim3(grid), dim3(256), 0, b->stream, A, part);
+    hipLaunchKernelGGL(k_les_flux_finish<NS>, dim3(1), dim3(64), 0, b->stream, (const double *)part, grid, row_dev);
+}
+
+extern "C" int x3d_les_scalar_flux(x3d_backend *b, const x3d_real *nut, x3d_real *const gphi[], int ns, const int dims[3],
+                                   const double *inv_prt, double *row_dev)
+{
+    X3D_RANGE(__func__);
+    X3D_REQUIRE(b && nut && gphi && dims && inv_prt && row_dev, "x3d_les_scalar_flux: null argument");
+    X3D_REQUIRE(ns >= 1 && ns <= 2, "x3d_les_scalar_flux: %d species in one call (1 or 2)", ns);
+    real_t *g[6];
+    for (int m = 0; m < 3 * ns; m++) {
+        X3D_REQUIRE(gphi[m], "x3d_les_scalar_flux: gradient block %d is null", m);
+        X3D_REQUIRE(gphi[m] != nut, "x3d_les_scalar_flux: gradient block %d and nu_t are the same block", m);
+        for (int q = 0; q < m; q++)
+            X3D_REQUIRE(gphi[m] != gphi[q], "x3d_les_scalar_flux: gradient blocks %d and %d are the same block", q, m);
+        g[m] = gphi[m];
+    }
+    X3D_REQUIRE(dims[0] > 0 && dims[1] > 0 && dims[2] > 0, "x3d_les_scalar_flux: dims (%d,%d,%d) must be positive", dims[0],
+                dims[1], dims[2]);
+    X3D_REQUIRE(dims[0] <= b->nxp && dims[1] <= b->nyp && dims[2] <= b->nzp,
+                "x3d_les_scalar_flux: dims (%d,%d,%d) outside the block", dims[0], dims[1], dims[2]);
+    for (int s = 0; s < ns; s++)
+        X3D_REQUIRE(inv_prt[s] > 0.0 && inv_prt[s] <= 1.79e308,
+                    "x3d_les_scalar_flux: 1 / Pr_t of species %d (%g) must be finite and positive", s, inv_prt[s]);
+    const int nchunk = (dims[0] + 256 * LES_V - 1) / (256 * LES_V);
+    const long nitem = (long)dims[1] * dims[2] * nchunk;
+    const int grid = (int)(nitem < LES_MAXWG ? nitem : LES_MAXWG);
+    // the partials live in the backend's reduction buffer, read as doubles
+    const long cap = (long)(sizeof(real_t) * 2 * (size_t)b->red_cap / sizeof(double));
+    X3D_REQUIRE((long)grid * ns <= cap, "x3d_les_scalar_flux: %d x %d partials, the reduction buffer holds %ld", grid, ns, cap);
+    X3D_LAZY_IN(b, nut);
+    for (int m = 0; m < 3 * ns; m++) X3D_LAZY_OUT(b, g[m], false);
+    X3D_LAZY_EAGER(b);
+    ProfScope ps(b, X3D_K_BLAS1);
+    if (ns == 1)
+        les_flux_launch<1>(b, nut, g, inv_prt, dims, grid, row_dev);
+    else
+        les_flux_launch<2>(b, nut, g, inv_prt, dims, grid, row_dev);
     X3D_HIP(hipGetLastError());
     return 0;
 }

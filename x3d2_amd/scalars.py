@@ -37,10 +37,15 @@ pbar the plane means of phi_s and q the plane means of (up . u) phi_s / |up|:
 All three are 1 for pure conduction.
 
 Refused, each an X3dError before anything is allocated or launched: no species; a list whose length is not nspecies; a value
-that is not finite; a wall value in a periodic direction; profile_dir not in (None, 2, 3); solver.les set; fields not at VERT.
+that is not finite; a wall value in a periodic direction; profile_dir not in (None, 2, 3); solver.les set to a model that
+does not serve species (les.Les with LesConfig(prt=...) does: its serves_species is true); fields not at VERT.
 
-Not built: Neumann (adiabatic) and Robin scalar walls; variable density beyond Boussinesq; a settling velocity; eddy
-diffusivity (LES refuses species); the Fortran shim's use; profile_dir = 1; scalar terms in Budgets; buoyancy fused into
+With such an LES model attached the species' right-hand side also gets the subgrid flux of the eddy diffusivity nu_t / Pr_t
+(Les.add).  The profiles and nu_vol below do NOT include that flux: they hold the resolved part only.  nu_lo / nu_hi are
+unaffected where nu_t vanishes at the wall, as WALE's does (Smagorinsky's does not, and has no wall damping here).
+
+Not built: Neumann (adiabatic) and Robin scalar walls; variable density beyond Boussinesq; a settling velocity; the
+subgrid flux in the flux profiles and nu_vol; the Fortran shim's use; profile_dir = 1; scalar terms in Budgets; buoyancy fused into
 transeq's z launch (a coupled run would then keep the deferred branch)."""
 import math
 
@@ -154,8 +159,10 @@ class Scalars:
         # ---- refusals: nothing is allocated or launched before the last of them
         if ns == 0:
             raise X3dError("Scalars: the solver transports no species (SolverConfig(n_species=...))")
-        if getattr(solver, "les", None) is not None:
-            raise X3dError("Scalars: an LES model is attached (eddy diffusivity for scalars is not built)")
+        les = getattr(solver, "les", None)
+        if les is not None and not getattr(les, "serves_species", False):
+            raise X3dError("Scalars: an LES model is attached that does not serve the species (Les with LesConfig(prt=...) "
+                           "adds their eddy diffusivity)")
         for name in ("ri", "ref", "grad", "wall", "init"):
             v = getattr(cfg, name)
             if v is not None and len(v) != ns:
