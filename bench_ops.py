@@ -81,8 +81,13 @@ field bytes the stencils ask for (order^3 x 3 values per particle); beside them 
 one from random order as one sample, then the median on the sorted state) and x3d_probe_sample for 4096 probes; (b) the choice
 of the default sort_every: 64 steps with 2^20 order-4 tracers at sort_every 0, 1, 8 and 64, HIP events around Particles.update
 (advance and the sorts that fall due), mean per step; (c) 20 fused RK3 steps with nothing attached, with Probes at every step
-(which gives up the more=True deferral as the particles do) and with 2^20 order-4 tracers (never sorted): wall time.  No gate.  The lines are
-appended to profiles/particles.jsonl.
+(which gives up the more=True deferral as the particles do) and with 2^20 order-4 tracers (never sorted): wall time.  No gate; (d)
+the launches of particles on several ranks, driven through the C ABI in this one process on a geometry that treats the box
+as the lower of two z slabs with itself as both neighbours (its own messages are what it receives), 2^20 order-4 tracers:
+ghost pack + unpack, move, emigrate + immigrate and sample, with the fused x3d_particles_advance timed in the same loop;
+gate t_move + t_sample <= 1.25 t_advance (the split reads and writes the twelve state rows once more: 192 B per particle
+against the 1536 B its stencils fetch, doubled for margin).  --particles-part mp runs (d) alone.  The lines are appended to
+profiles/particles.jsonl.
 
 --family scalars (csrc/scalars.hip, x3d2_amd/scalars.py), at --snap-n (512) cubed, HIP events, the two sides of a comparison
 timed in turn inside one loop: (a) x3d_scalars_couple at ns = 1, up = y next to x3d_vecadd on the same blocks (both move three
@@ -1123,7 +1128,7 @@ def bench_particles(args):
     s = case.solver
     b = s.backend
     case.run(n_iters=3)
-    for log2 in (16, 20, 22):
+    for log2 in (() if args.particles_part == "mp" else (16, 20, 22)):
         npart = 1 << log2
         x0 = seed_uniform(s.mesh, npart, seed=1)
         for order in (2, 4):
@@ -1147,6 +1152,9 @@ def bench_particles(args):
                 emit(dict({"op": "x3d_particles_sort of a sorted state: keys + radix sort + gather", "particles": npart, "order": order,
                            "kind": kind}, **t))
                 del p
+    bench_particles_mp(args, emit, s)
+    if args.particles_part == "mp":
+        return
     pts = seed_uniform(s.mesh, 4096, seed=2)
     pr = Probes(s, ProbesConfig(pts, prefix=os.path.join(tmp, "probes")))
     row = torch.zeros(3 * 4096, dtype=torch.float64, device=b.device)
@@ -1193,6 +1201,84 @@ def bench_particles(args):
     for what in ("probes", "particles"):
         emit({"op": "TGV, fused, RK3: 20 steps, %s" % what, "wall_ms_without": res["nothing"], "wall_ms_with": res[what],
               "ms_per_step_without": res["nothing"] / 20.0, "added_ms_per_step": (res[what] - res["nothing"]) / 20.0})
+
+
+def bench_particles_mp(args, emit, s):
+    """(d) of the "particles" family: the launches of a several-rank advance beside the fused one-rank launch, in one loop"""
+    import ctypes
+
+    import torch
+    from x3d2_amd import _lib
+    from x3d2_amd.diagnostics import global_vert_coords
+    from x3d2_amd.particles import DP, Particles, ParticlesConfig, seed_uniform
+    b, m, lib = s.backend, s.mesh, s.backend.lib
+    n, rb, npart, order, gh = [int(v) for v in m.vert_dims], 4 if _lib.SINGLE else 8, 1 << 20, 4, 2
+    x0 = seed_uniform(m, npart, seed=1)
+    fused = Particles(s, ParticlesConfig(x0, order=order, sort_every=0))
+    # the box as rank 0 of two z slabs: the z table runs on over a second box, the period doubles
+    coords = [np.ascontiguousarray(global_vert_coords(m, d), dtype=np.float64) for d in range(3)]
+    coords[2] = np.concatenate([coords[2], coords[2] + float(m.L[2])])
+    prm, dc = _lib.ParticlesParams(), _lib.ParticlesDecomp()
+    prm.n, prm.order, prm.wall, prm.tau = 2 * npart, order, 0, 0.0
+    for d in range(3):
+        prm.periodic[d], prm.uniform[d], prm.L[d] = 1, 1, float(m.L[d]) * (2 if d == 2 else 1)
+        prm.coords[d] = coords[d].ctypes.data_as(DP)
+        dc.nglobal[d], dc.offset[d], dc.nlocal[d], dc.nproc[d], dc.rank[d] = n[d] * (2 if d == 2 else 1), 0, n[d], 2 if d == 2 else 1, 0
+    dc.capacity, dc.mig_capacity = ParticlesConfig(np.zeros((2 * npart, 3))).capacities(2)
+    ids = np.arange(npart, dtype=np.int32)
+    xt = np.ascontiguousarray(x0.T)
+    h = ctypes.c_void_p()
+    _lib.check(lib.x3d_particles_mp_create(b.h, ctypes.byref(prm), ctypes.byref(dc), xt.ctypes.data_as(DP), None,
+                                           ids.ctypes.data_as(_lib.c_int_p), npart, ctypes.byref(h)))
+    real = torch.float64 if rb == 8 else torch.float32
+    nr = n[1] + 1 + gh
+    ghost_lo = torch.zeros(3 * gh * nr * n[0], dtype=real, device=b.device)  # to pprev = what pnext sends = this rank's own
+    ghost_hi = torch.zeros(3 * nr * n[0], dtype=real, device=b.device)
+    mig = [torch.zeros(1 + 13 * dc.mig_capacity, dtype=torch.float64, device=b.device) for _ in range(2)]
+    fields = (s.u.ptr, s.v.ptr, s.w.ptr, b._dims(0))
+    dt = float(s.dt)
+
+    def ghosts():
+        _lib.check(lib.x3d_particles_mp_ghost_pack(b.h, h, 3, *fields, ghost_lo.data_ptr(), ghost_hi.data_ptr()))
+        _lib.check(lib.x3d_particles_mp_ghost_unpack(b.h, h, 3, ghost_hi.data_ptr(), ghost_lo.data_ptr()))
+
+    def migrate():
+        _lib.check(lib.x3d_particles_mp_emigrate(b.h, h, 3, mig[0].data_ptr(), mig[1].data_ptr()))
+        _lib.check(lib.x3d_particles_mp_immigrate(b.h, h, 3, mig[1].data_ptr(), mig[0].data_ptr()))
+
+    ghosts()
+    _lib.check(lib.x3d_particles_mp_prime(b.h, h, *fields))
+    stages = [("x3d_particles_advance (fused, one rank)", lambda: fused.advance(s.u, s.v, s.w, dt)),
+              ("x3d_particles_mp_move", lambda: _lib.check(lib.x3d_particles_mp_move(b.h, h, dt))),
+              ("x3d_particles_mp_emigrate + immigrate (z)", migrate),
+              ("x3d_particles_mp_ghost_pack + unpack (z)", ghosts),
+              ("x3d_particles_mp_sample", lambda: _lib.check(lib.x3d_particles_mp_sample(b.h, h, *fields)))]
+    ms, times = ctypes.c_float(), {name: [] for name, _ in stages}
+    for i in range(args.stat_warmup + args.stat_iters):
+        for name, fn in stages:
+            _lib.check(lib.x3d_timer_start(b.h))
+            fn()
+            _lib.check(lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+            if i >= args.stat_warmup:
+                times[name].append(ms.value)
+    q = (ctypes.c_int * 2)()
+    _lib.check(lib.x3d_particles_mp_query(b.h, h, q))
+    t = {name: spread(v) for name, v in times.items()}
+    face_bytes = (ghost_lo.numel() + ghost_hi.numel()) * rb
+    for name, _ in stages:
+        row = {"op": name + ", random order", "particles": npart, "order": order, "kind": "tracers"}
+        if "ghost" in name:
+            row["face_bytes_per_direction"] = face_bytes
+        if "migrate" in name or "emigrate" in name:
+            row["message_bytes"] = 2 * mig[0].numel() * 8
+        emit(dict(row, **t[name]))
+    adv, split = t[stages[0][0]]["ms_median"], t[stages[1][0]]["ms_median"] + t[stages[4][0]]["ms_median"]
+    emit({"op": "gate: t_move + t_sample <= 1.25 t_advance", "particles": npart, "order": order, "kind": "tracers", "ms_advance": adv,
+          "ms_move_plus_sample": split, "ratio": split / adv, "passed": bool(split <= 1.25 * adv),
+          "added_ms_per_step_migrate": t[stages[2][0]]["ms_median"], "added_ms_per_step_ghosts": t[stages[3][0]]["ms_median"],
+          "residents_after": int(q[0]), "flags_after": int(q[1])})
+    _lib.check(lib.x3d_particles_destroy(h))
+    del fused
 
 
 def bench_scalars(args):
@@ -1308,6 +1394,7 @@ def main():
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
+    ap.add_argument("--particles-part", default="all", choices=("all", "mp"))  # family particles: everything, or (d) alone
     args = ap.parse_args()
     if args.family in ("all", "stats"):
         bench_stats(args)

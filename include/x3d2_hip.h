@@ -1091,6 +1091,74 @@ int x3d_particles_pack(x3d_backend *b, const x3d_particles *p, void *dst_dev, lo
 int x3d_particles_download(x3d_backend *b, const x3d_particles *p, double *rows, int *id, int *status, int *has_history);
 int x3d_particles_upload(x3d_backend *b, x3d_particles *p, const double *rows, const int *id, const int *status, int has_history);
 
+/* ---- particles on several ranks (csrc/particles.hip).  Not in the reference.  y and z may be cut, x never is.  A rank holds
+ * the particles it OWNS: rank r of a cut direction owns c[r nl] <= x < c[(r + 1) nl] on the GLOBAL table c, the last rank up to
+ * L (periodic) or up to and including the last vertex; a particle of status 2 stays where it died.  The state is `capacity`
+ * slots per row, the local count is a device word, every launch covers the slots and leaves at t >= count.  An advance is
+ *    move  ->  per cut direction, y then z: emigrate, exchange, immigrate  ->  per cut direction: ghost_pack, exchange,
+ *    ghost_unpack  ->  sample
+ * with the exchanges (fixed-size messages to / from the ring neighbours pprev and pnext) left to the caller.  None of these
+ * waits for the host except query, download and upload.  The handle is destroyed with x3d_particles_destroy; the one-rank
+ * entry points refuse such a handle and these refuse a one-rank one.  dir is 2 (y) or 3 (z) and must be cut.  A bad argument
+ * is an error and launches nothing.
+ *
+ * Sticky flags (query, download): nothing is written out of bounds and nothing is lost silently.
+ *   MIG  more leavers to one neighbour than mig_capacity: ALL leavers to that neighbour stayed where they were
+ *   CAP  more residents than capacity: the arrivals that did not fit were not taken
+ *   FAR  a particle is owned neither here nor by a ring neighbour of the direction: it stayed where it was */
+enum { X3D_PARTICLES_FLAG_MIG = 1, X3D_PARTICLES_FLAG_CAP = 2, X3D_PARTICLES_FLAG_FAR = 4 };
+typedef struct x3d_particles_decomp {
+    int nglobal[3];             /* global vertices: the length of x3d_particles_params.coords[d] */
+    int offset[3], nlocal[3];   /* this rank's first global vertex and its count (the backend's nx, ny, nz) */
+    int nproc[3], rank[3];      /* ranks along each direction (nproc[0] = 1) and this rank's position: 0 and nproc - 1 sit at the
+                                   global ends; a cut direction needs nlocal >= 4 */
+    int capacity, mig_capacity; /* slots of the state; slots of one migration message */
+} x3d_particles_decomp;
+/* prm->n is the GLOBAL count and prm->coords the global tables; x0[3][m], v0[3][m] (or NULL), id[m]: this rank's m particles
+ * (m may be 0), periodic coordinates are wrapped on the host; a particle this rank does not own is an error. */
+int x3d_particles_mp_create(x3d_backend *b, const x3d_particles_params *prm, const x3d_particles_decomp *dc, const double *x0,
+                            const double *v0, const int *id, int m, x3d_particles **out);
+/* one launch: the face planes of u, v, w that the neighbours' stencils reach.  With gh = 2 (order 4) or 1 (order 2) planes
+ * above and 1 below: send_prev[3][gh][nr][nx] the lowest planes, send_next[3][1][nr][nx] the highest; y: nr = nz; z: nr =
+ * ny + 1 + gh rows, the y ghosts included (do y first), so that the edges of a pencil need no diagonal message.  The interior
+ * is never copied. */
+int x3d_particles_mp_ghost_pack(x3d_backend *b, x3d_particles *p, int dir, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                                const int dims[3], x3d_real *send_prev, x3d_real *send_next);
+/* one launch: recv_prev[3][1][nr][nx] (pprev's send_next) and recv_next[3][gh][nr][nx] (pnext's send_prev) into the frame the
+ * particles own.  At a global non-periodic end the stencil is one-sided and never reads what the ring delivered there. */
+int x3d_particles_mp_ghost_unpack(x3d_backend *b, x3d_particles *p, int dir, const x3d_real *recv_prev, const x3d_real *recv_next);
+/* x3d_particles_prime through the ghost-aware rows: the frames must be current. */
+int x3d_particles_mp_prime(x3d_backend *b, x3d_particles *p, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                           const int dims[3]);
+/* one launch, the first half of x3d_particles_advance with the same expressions: new x [and v], finiteness test, wrap and wall
+ * rule, v_prev <- v [v <- v_new, F_prev <- F]. */
+int x3d_particles_mp_move(x3d_backend *b, x3d_particles *p, double dt);
+/* one launch, the second half: a = u(x); tracers v = a; inertial F = (a - v) / tau + g. */
+int x3d_particles_mp_sample(x3d_backend *b, x3d_particles *p, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                            const int dims[3]);
+/* three launches (classes and block counts; one block's scan; scatter), no floating-point atomics, every slot a function of
+ * the input order alone: the stayers to the front in their order, the leavers as whole rows into the messages.  A message is
+ * 1 + (nrow + 1) mig_capacity doubles: the count (int64), [nrow][mig_capacity] doubles, id and status [2][mig_capacity] ints. */
+int x3d_particles_mp_emigrate(x3d_backend *b, x3d_particles *p, int dir, double *send_prev, double *send_next);
+/* one launch: the arrivals behind the stayers, those from pprev (its send_next) first, then those from pnext, each in the
+ * sender's order; the count is updated on the device. */
+int x3d_particles_mp_immigrate(x3d_backend *b, x3d_particles *p, int dir, const double *recv_prev, const double *recv_next);
+/* x3d_particles_sort on the local cell key ((k - off_z) ny + (j - off_y)) nx + i over `capacity` slots: particles that are
+ * not alive next to last, empty slots last. */
+int x3d_particles_mp_sort(x3d_backend *b, x3d_particles *p);
+/* out[0] the local count, out[1] the flags; waits for the stream. */
+int x3d_particles_mp_query(x3d_backend *b, const x3d_particles *p, int out[2]);
+/* one launch: x, v, a (9 rows of `capacity` doubles), id, status (2 rows of `capacity` ints), the local count and the flags (2 ints) into
+ * dst_dev (80 capacity + 8 bytes, 8-byte aligned), in device order; waits on the device like x3d_particles_pack. */
+int x3d_particles_mp_pack(x3d_backend *b, const x3d_particles *p, void *dst_dev, long capacity);
+/* the local state to / from host arrays in device order, rows[12 or 18][n_local] densely (room for `capacity` is needed);
+ * both wait for the stream.  upload takes m <= capacity particles this rank owns (distinct ids of 0..n-1), checks what create
+ * checks, and clears the flags. */
+int x3d_particles_mp_download(x3d_backend *b, const x3d_particles *p, double *rows, int *id, int *status, int *n_local, int *flags,
+                              int *has_history);
+int x3d_particles_mp_upload(x3d_backend *b, x3d_particles *p, const double *rows, const int *id, const int *status, int m,
+                            int has_history);
+
 /* ---- active scalars (csrc/scalars.hip).  Not in the reference: this project's own addition.  With ns species phi_s:
  *    d_i      +=  up_i sum_s ri_s (phi_s - ref_s)                i = x, y, z     (Boussinesq buoyancy)
  *    dphi_s   +=  -(G_s,x u + G_s,y v + G_s,z w)                                 (imposed mean scalar gradient)

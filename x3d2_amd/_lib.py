@@ -292,6 +292,19 @@ PROTOTYPES = {
     "x3d_particles_pack": (I, [VP, VP, VP, ctypes.c_long]),
     "x3d_particles_download": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, c_int_p]),
     "x3d_particles_upload": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, I]),
+    "x3d_particles_mp_create": (I, [VP, VP, VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int_p, I, ctypes.POINTER(VP)]),
+    "x3d_particles_mp_ghost_pack": (I, [VP, VP, I, VP, VP, VP, c_int_p, VP, VP]),
+    "x3d_particles_mp_ghost_unpack": (I, [VP, VP, I, VP, VP]),
+    "x3d_particles_mp_prime": (I, [VP, VP, VP, VP, VP, c_int_p]),
+    "x3d_particles_mp_move": (I, [VP, VP, ctypes.c_double]),
+    "x3d_particles_mp_sample": (I, [VP, VP, VP, VP, VP, c_int_p]),
+    "x3d_particles_mp_emigrate": (I, [VP, VP, I, VP, VP]),
+    "x3d_particles_mp_immigrate": (I, [VP, VP, I, VP, VP]),
+    "x3d_particles_mp_sort": (I, [VP, VP]),
+    "x3d_particles_mp_query": (I, [VP, VP, c_int_p]),
+    "x3d_particles_mp_pack": (I, [VP, VP, VP, ctypes.c_long]),
+    "x3d_particles_mp_download": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "x3d_particles_mp_upload": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, I, I]),
     "x3d_scalars_couple": (I, [VP, ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), c_int_p, VP]),
     "x3d_scalars_apply_bc": (I, [VP, ctypes.POINTER(VP), I, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_double), I]),
     "x3d_scalars_profile_sums": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), I, c_int_p, I, VP, VP]),
@@ -325,6 +338,12 @@ class ScalarsParams(ctypes.Structure):
     """x3d_scalars_params of include/x3d2_hip.h"""
     _fields_ = [("ns", I), ("up", ctypes.c_double * 3), ("ri", ctypes.POINTER(ctypes.c_double)),
                 ("ref", ctypes.POINTER(ctypes.c_double)), ("grad", ctypes.POINTER(ctypes.c_double))]
+
+
+class ParticlesDecomp(ctypes.Structure):
+    """x3d_particles_decomp of include/x3d2_hip.h"""
+    _fields_ = [("nglobal", I * 3), ("offset", I * 3), ("nlocal", I * 3), ("nproc", I * 3), ("rank", I * 3), ("capacity", I),
+                ("mig_capacity", I)]
 
 
 class ParticlesParams(ctypes.Structure):

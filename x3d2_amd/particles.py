@@ -34,8 +34,31 @@ Output: every ipartout steps one pack launch and one asynchronous copy through c
 `<prefix>_<it:06d>.npz` (id, x[n, 3], v, a, alive, status, iteration, time, in id order) once the copy has landed; write never
 waits for the host.  state() is the same content now, with one host wait.
 
-One rank only."""
+Several ranks (y and / or z cut; x never is).  A rank holds the particles it OWNS: rank r of a cut direction owns
+c[r nl] <= x < c[(r + 1) nl] on the global vertex table, the last rank up to L (periodic) or up to and including the last
+vertex (owner_index below; csrc/particles.hip holds the same comparisons on the same doubles); absorbed particles are owned by
+position like any other, a particle whose position stopped being finite stays where it died.  cfg.x0 / v0 are the same global
+arrays on every rank, each keeps its rows, id is the global row.  An advance is then
+
+  move      one launch: the position (velocity) update, finiteness test, wrap, wall rule, v_prev <- v [v <- v_new, F_prev <- F]
+  migrate   per cut direction, y then z: classification and a deterministic compaction on the device (stayers to the front in
+            their order, leavers as whole rows into two messages of mig_capacity slots with their count in a header word),
+            Comm.sendrecv with pprev / pnext, one launch that appends the arrivals: from pprev, then from pnext
+  ghosts    per cut direction, y then z (z on rows that include the y ghosts): the face planes of u, v, w the stencil reaches
+            (order 4: one below, two above; order 2: one above, and one below that keeps every message non-empty), never
+            the interior
+  sample    one launch: a = u(x) through rows of the block or of a ghost frame; v or F from it
+
+with no host wait of its own (a host-staged transport waits in sendrecv).  The state has `capacity` slots
+(default ceil(1.5 n / nproc) + 1024) and a message `mig_capacity` (default max(1024, capacity // 8)): this project's choice.
+More leavers than mig_capacity, more residents than capacity, or a particle owned neither here nor by a ring neighbour set a
+sticky device flag and keep the particle where it is; state(), raw_state(), state_dict(), check() and the file writer raise an
+X3dError that names the cause and the rank.  state() is collective and returns the global state on every rank; files are
+`<prefix>_<it:06d>.r<rank>.npz`, which load_particles assembles; interpolate is refused."""
 import ctypes
+import glob
+import math
+import os
 
 import numpy as np
 
@@ -48,16 +71,20 @@ MAX_PARTICLES = 1 << 24  # X3D_PARTICLES_MAX of include/x3d2_hip.h
 WALLS = {"reflect": 0, "absorb": 1}
 DP = ctypes.POINTER(ctypes.c_double)
 ROWS = ("x", "v", "a", "v_prev", "F", "F_prev")  # three rows each; tracers hold the first four
+FLAGS = ((1, "more leavers than mig_capacity in one step (they stayed on this rank)"),
+         (2, "more residents than capacity (arrivals that did not fit were not taken)"),
+         (4, "a particle is owned neither by this rank nor by a neighbour of the direction it left in"))
 
 
 class ParticlesConfig:
     """x0: [n, 3] start positions, 1 <= n <= 2^24; order 2 or 4; tau_p = 0: tracers; v0: [n, 3] start velocities of
     inertial particles (None: the fluid's); wall: "reflect" or "absorb"; advance from iteration initpart on (<= 0: never);
     a file every ipartout iterations (0: none); sort by cell every sort_every iterations (0: never; 8 is the measured
-    minimum of advance plus amortised sort, README)"""
+    minimum of advance plus amortised sort, README); several ranks: capacity slots of state per rank (None:
+    ceil(1.5 n / nproc) + 1024) and mig_capacity slots per migration message (None: max(1024, capacity // 8))"""
 
     def __init__(self, x0, order=4, tau_p=0.0, gravity=(0.0, 0.0, 0.0), v0=None, wall="reflect", initpart=1, ipartout=0,
-                 prefix="particles", sort_every=8):
+                 prefix="particles", sort_every=8, capacity=None, mig_capacity=None):
         x = np.array(x0, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != 3 or not 1 <= x.shape[0] <= MAX_PARTICLES:
             raise X3dError("ParticlesConfig: x0 is an [n, 3] array of positions, 1 <= n <= %d" % MAX_PARTICLES)
@@ -89,6 +116,17 @@ class ParticlesConfig:
         if self.ipartout < 0 or self.sort_every < 0:
             raise X3dError("ParticlesConfig: ipartout and sort_every must not be negative")
         self.prefix = str(prefix)
+        self.capacity = None if capacity is None else int(capacity)
+        self.mig_capacity = None if mig_capacity is None else int(mig_capacity)
+        if (self.capacity is not None and not 1 <= self.capacity <= MAX_PARTICLES) or \
+                (self.mig_capacity is not None and self.mig_capacity < 1):
+            raise X3dError("ParticlesConfig: capacity is 1 to %d, mig_capacity at least 1" % MAX_PARTICLES)
+
+    def capacities(self, nproc):
+        """(capacity, mig_capacity) on `nproc` ranks"""
+        cap = self.capacity if self.capacity is not None else min(MAX_PARTICLES, int(math.ceil(1.5 * self.n / nproc)) + 1024)
+        mig = self.mig_capacity if self.mig_capacity is not None else max(1024, cap // 8)
+        return cap, mig  # (a message has one length on every rank, whatever the rank's own capacity)
 
     @property
     def n(self):
@@ -123,8 +161,29 @@ def seed_uniform(mesh, n, seed=0):
     return out
 
 
-def file_name(prefix, it):
-    return "%s_%06d.npz" % (prefix, int(it))
+def wrap(x, L):
+    """part_wrap of csrc/particles.hip, as the host applies it before it asks who owns a start position"""
+    x = np.asarray(x, dtype=np.float64)
+    y = x - L * np.floor(x / L)
+    y = np.where(y >= L, 0.0, y)
+    return np.where(y < 0.0, 0.0, y)
+
+
+def owner_index(c, nproc, periodic, L, x):
+    """the position along one direction of the rank that owns each (wrapped, in-domain) coordinate of x: rank r owns
+    c[r nl] <= x < c[(r + 1) nl], the last rank up to L (periodic) or up to and including the last vertex; -1: nobody"""
+    c, x = np.asarray(c, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    nl = c.size // int(nproc)
+    out = np.full(x.shape, -1, dtype=np.int64)
+    for r in range(int(nproc)):
+        own = x >= c[r * nl]
+        own &= ((x < L) if periodic else (x <= c[-1])) if r == nproc - 1 else (x < c[(r + 1) * nl])
+        out[own] = r
+    return out
+
+
+def file_name(prefix, it, rank=None):
+    return "%s_%06d.npz" % (prefix, int(it)) if rank is None else "%s_%06d.r%d.npz" % (prefix, int(it), int(rank))
 
 
 def by_id(id_, *arrays):
@@ -133,22 +192,36 @@ def by_id(id_, *arrays):
     return [np.ascontiguousarray(np.asarray(a)[..., order]) for a in arrays]
 
 
-def unpack(raw, n):
-    """the bytes x3d_particles_pack wrote -> dict of id, x, v, a [n, 3], alive, status in id order"""
+def unpack(raw, n, sorted_ids=False):
+    """the bytes x3d_particles_pack wrote -> dict of id, x, v, a [n, 3], alive, status in id order (sorted_ids: the ids are
+    a rank's own, not 0..n-1)"""
     raw = np.asarray(raw)
     rows = raw[:72 * n].view(np.float64).reshape(9, n)
     ints = raw[72 * n:80 * n].view(np.int32).reshape(2, n)
     rows, status = by_id(ints[0], rows, ints[1])
-    return {"id": np.arange(n, dtype=np.int64), "x": rows[0:3].T.copy(), "v": rows[3:6].T.copy(), "a": rows[6:9].T.copy(),
+    return {"id": np.sort(ints[0]).astype(np.int64) if sorted_ids else np.arange(n, dtype=np.int64), "x": rows[0:3].T.copy(), "v": rows[3:6].T.copy(), "a": rows[6:9].T.copy(),
             "alive": (status == 1).astype(np.int32), "status": status.astype(np.int32)}
 
 
 def load_particles(prefix, it):
     """the file write(it) left, as a dict (id order): id, x, v, a, alive, status, iteration, time"""
     name = file_name(prefix, it)
+    parts = [] if os.path.exists(name) else sorted(glob.glob(glob.escape(name[:-4]) + ".r*.npz"))
     try:
-        with np.load(name, allow_pickle=False) as z:
-            out = {k: z[k] for k in z.files}
+        if parts:  # the pieces of a decomposed run, assembled in id order
+            pieces = []
+            for q in parts:
+                with np.load(q, allow_pickle=False) as z:
+                    pieces.append({k: z[k] for k in z.files})
+            ids = np.concatenate([q["id"] for q in pieces])
+            order = np.argsort(ids, kind="stable")
+            if not np.array_equal(ids[order], np.arange(ids.size)):
+                raise ValueError("the ids of the pieces are not 0..n-1, each once")
+            out = {k: (np.concatenate([q[k] for q in pieces])[order] if np.ndim(v) else v) for k, v in pieces[0].items()}
+            name = name[:-4] + ".r<rank>.npz"
+        else:
+            with np.load(name, allow_pickle=False) as z:
+                out = {k: z[k] for k in z.files}
     except Exception as e:
         raise X3dError("load_particles: cannot read %s: %s: %s" % (name, type(e).__name__, e))
     for k in ("id", "x", "v", "a", "alive", "iteration", "time"):
@@ -168,6 +241,8 @@ def check_state_dict(z, n, order, tau_p):
         raise X3dError("restore: particles_tau_p differs: the checkpoint has %r, this run %r" % (float(z["particles_tau_p"]), float(tau_p)))
     nrow = 18 if tau_p > 0.0 else 12
     rows, status = np.asarray(z["particles_rows"]), np.asarray(z["particles_status"])
+    if "particles_id" in z:  # a rank's own particles of a decomposed run
+        n = int(np.asarray(z["particles_id"]).size)
     if rows.shape != (nrow, n) or rows.dtype != np.float64 or status.shape != (n,):
         raise X3dError("restore: particles_rows is %s %s, this run needs float64 %s" % (rows.dtype.name, rows.shape, (nrow, n)))
 
@@ -179,11 +254,20 @@ class Particles:
     def __init__(self, solver, cfg):
         self.solver, self.cfg = solver, cfg
         b, m = solver.backend, solver.mesh
-        if int(m.nproc) != 1:
-            raise X3dError("Particles: multi-rank particles are not built")
+        self.mp = int(m.nproc) != 1
+        self.rank, self.comm = int(m.nrank), b.comm
         self.n, self.nrow = cfg.n, 18 if cfg.inertial else 12
         dims = [int(v) for v in m.get_dims(VERT)]
-        if cfg.order == 4 and min(dims) < 4:
+        if self.mp:
+            if int(m.nproc_dir[0]) > 1:
+                raise X3dError("Particles: x is never cut (nproc_dir[0] = %d)" % int(m.nproc_dir[0]))
+            for d in (1, 2):
+                if int(m.nproc_dir[d]) > 1 and dims[d] < 4:
+                    raise X3dError("Particles: a rank needs at least 4 vertices in a cut direction, direction %d has %d" % (d + 1, dims[d]))
+            if int(getattr(b.comm, "size", 1)) != int(m.nproc):
+                raise X3dError("Particles: the mesh is cut into %d ranks, the backend's communicator has %d: multi-rank particles "
+                               "are not built without one process per rank" % (int(m.nproc), int(getattr(b.comm, "size", 1))))
+        if cfg.order == 4 and min(int(v) for v in m.global_vert_dims) < 4:
             raise X3dError("Particles: order 4 needs at least 4 vertices per direction")
         if cfg.inertial and cfg.tau_p < 2.0 * float(solver.dt):
             raise X3dError("Particles: 0 < tau_p < 2 dt is refused (AB2 on the drag term needs dt / tau_p <= 0.5)")
@@ -196,15 +280,61 @@ class Particles:
             prm.uniform[d] = int(not m.stretched[d])
             prm.L[d] = float(m.L[d])
             prm.coords[d] = self.coords[d].ctypes.data_as(DP)
-        x0 = np.ascontiguousarray(cfg.x0.T)
-        v0 = np.ascontiguousarray(cfg.v0.T) if cfg.v0 is not None else None
         self.lib, self.h = b.lib, ctypes.c_void_p()
-        _lib.check(b.lib.x3d_particles_create(b.h, ctypes.byref(prm), x0.ctypes.data_as(DP),
-                                              v0.ctypes.data_as(DP) if v0 is not None else None, ctypes.byref(self.h)))
+        if self.mp:
+            self._create_mp(prm, dims)
+        else:
+            x0 = np.ascontiguousarray(cfg.x0.T)
+            v0 = np.ascontiguousarray(cfg.v0.T) if cfg.v0 is not None else None
+            _lib.check(b.lib.x3d_particles_create(b.h, ctypes.byref(prm), x0.ctypes.data_as(DP),
+                                                  v0.ctypes.data_as(DP) if v0 is not None else None, ctypes.byref(self.h)))
         self.ring = CopyRing(b, 2, self._write_file)  # (nothing is allocated until the first write)
         self.files = []
         self.iteration = int(solver.current_iter)  # the iteration the state belongs to
         self.prime()
+
+    def owned(self, x):
+        """which of the (wrapped) positions x [m, 3] this rank owns"""
+        m = self.solver.mesh
+        mask = np.ones(x.shape[0], dtype=bool)
+        for d in (1, 2):
+            if int(m.nproc_dir[d]) > 1:
+                mask &= owner_index(self.coords[d], int(m.nproc_dir[d]), bool(m.periodic_BC[d]), float(m.L[d]), x[:, d]) == \
+                    int(m.nrank_dir[d])
+        return mask
+
+    def _create_mp(self, prm, dims):
+        import torch
+        b, m, cfg = self.solver.backend, self.solver.mesh, self.cfg
+        x = cfg.x0.copy()
+        for d in range(3):
+            if m.periodic_BC[d]:
+                x[:, d] = wrap(x[:, d], float(m.L[d]))
+        ids = np.ascontiguousarray(np.nonzero(self.owned(x))[0], dtype=np.int32)
+        self.capacity, self.mig_capacity = cfg.capacities(int(m.nproc))
+        if ids.size > self.capacity:
+            raise X3dError("Particles: rank %d owns %d particles at the start, capacity is %d" % (self.rank, ids.size, self.capacity))
+        dc = _lib.ParticlesDecomp()
+        for d in range(3):
+            dc.nglobal[d], dc.offset[d], dc.nlocal[d] = int(m.global_vert_dims[d]), int(m.n_offset[d]), dims[d]
+            dc.nproc[d], dc.rank[d] = int(m.nproc_dir[d]), int(m.nrank_dir[d])
+        dc.capacity, dc.mig_capacity = self.capacity, self.mig_capacity
+        x0 = np.ascontiguousarray(x[ids].T)
+        v0 = np.ascontiguousarray(cfg.v0[ids].T) if cfg.v0 is not None else None
+        _lib.check(b.lib.x3d_particles_mp_create(b.h, ctypes.byref(prm), ctypes.byref(dc), x0.ctypes.data_as(DP),
+                                                 v0.ctypes.data_as(DP) if v0 is not None else None,
+                                                 ids.ctypes.data_as(_lib.c_int_p), int(ids.size), ctypes.byref(self.h)))
+        # the messages: per cut direction (to pprev, to pnext, from pprev, from pnext)
+        real = torch.float64 if np.dtype(_lib.NP_REAL) == np.dtype(np.float64) else torch.float32
+        gh, nx, ny, nz = (2 if cfg.order == 4 else 1), dims[0], dims[1], dims[2]
+        self.dirs = [d for d in (1, 2) if int(m.nproc_dir[d]) > 1]
+        self.ghost_buf, self.mig_buf = {}, {}
+        for d in self.dirs:
+            nr = nz if d == 1 else ny + 1 + gh
+            lo, hi = 3 * gh * nr * nx, 3 * nr * nx  # (what goes down serves the neighbour's gh planes above)
+            self.ghost_buf[d] = tuple(torch.zeros(k, dtype=real, device=b.device) for k in (lo, hi, hi, lo))
+            self.mig_buf[d] = tuple(torch.zeros(1 + (self.nrow + 1) * self.mig_capacity, dtype=torch.float64, device=b.device)
+                                    for _ in range(4))
 
     def __del__(self):
         try:
@@ -223,23 +353,56 @@ class Particles:
         b._need_vert("Particles", u, v, w)
         return u.ptr, v.ptr, w.ptr, b._dims(VERT)
 
+    def _ghosts(self, ptrs):
+        """the face planes the stencil reaches, y then z: pack, exchange, unpack"""
+        b, m = self.solver.backend, self.solver.mesh
+        for d in self.dirs:
+            ss, se, rs, re = self.ghost_buf[d]
+            _lib.check(self.lib.x3d_particles_mp_ghost_pack(b.h, self.h, d + 1, *ptrs, ss.data_ptr(), se.data_ptr()))
+            self.comm.sendrecv([(ss, se, rs, re)], int(m.pprev[d]), int(m.pnext[d]))
+            _lib.check(self.lib.x3d_particles_mp_ghost_unpack(b.h, self.h, d + 1, rs.data_ptr(), re.data_ptr()))
+
+    def _migrate(self):
+        b, m = self.solver.backend, self.solver.mesh
+        for d in self.dirs:
+            ss, se, rs, re = self.mig_buf[d]
+            _lib.check(self.lib.x3d_particles_mp_emigrate(b.h, self.h, d + 1, ss.data_ptr(), se.data_ptr()))
+            self.comm.sendrecv([(ss, se, rs, re)], int(m.pprev[d]), int(m.pnext[d]))
+            _lib.check(self.lib.x3d_particles_mp_immigrate(b.h, self.h, d + 1, rs.data_ptr(), re.data_ptr()))
+
     def prime(self):
         """a = u(x) from the solver's fields as they are; v and F from it.  The next advance is a first one."""
         s = self.solver
         s.flush_grad()  # a velocity correction left pending by step(more=True) is not in u, v, w yet
-        _lib.check(self.lib.x3d_particles_prime(s.backend.h, self.h, *self._fields(s.u, s.v, s.w)))
+        ptrs = self._fields(s.u, s.v, s.w)
+        if self.mp:
+            self._ghosts(ptrs)
+            _lib.check(self.lib.x3d_particles_mp_prime(s.backend.h, self.h, *ptrs))
+        else:
+            _lib.check(self.lib.x3d_particles_prime(s.backend.h, self.h, *ptrs))
 
     def advance(self, u, v, w, dt):
-        """one launch on fields of the caller's"""
-        _lib.check(self.lib.x3d_particles_advance(self.solver.backend.h, self.h, *self._fields(u, v, w), float(dt)))
+        """one launch on fields of the caller's; several ranks: move, migrate, ghosts, sample (collective)"""
+        b = self.solver.backend
+        ptrs = self._fields(u, v, w)
+        if not self.mp:
+            _lib.check(self.lib.x3d_particles_advance(b.h, self.h, *ptrs, float(dt)))
+            return
+        _lib.check(self.lib.x3d_particles_mp_move(b.h, self.h, float(dt)))
+        self._migrate()
+        self._ghosts(ptrs)
+        _lib.check(self.lib.x3d_particles_mp_sample(b.h, self.h, *ptrs))
 
     def sort(self):
-        _lib.check(self.lib.x3d_particles_sort(self.solver.backend.h, self.h))
+        f = self.lib.x3d_particles_mp_sort if self.mp else self.lib.x3d_particles_sort
+        _lib.check(f(self.solver.backend.h, self.h))
 
     def interpolate(self, points, u, v, w):
         """[m, 3] values of (u, v, w) at the [m, 3] points: one launch, one host wait.  A point outside a non-periodic
         direction's [first, last vertex] or one that is not finite is an error."""
         import torch
+        if self.mp:
+            raise X3dError("Particles.interpolate: not built on several ranks")
         b = self.solver.backend
         pts = np.array(points, dtype=np.float64)
         if pts.ndim != 2 or pts.shape[1] != 3 or not 1 <= pts.shape[0] <= MAX_PARTICLES:
@@ -287,17 +450,27 @@ class Particles:
         if it != self.iteration:
             raise X3dError("Particles.write: iteration %d, the state is at %d" % (it, self.iteration))
         b = self.solver.backend
-        nbytes = 80 * self.n
+        nbytes = 80 * self.capacity + 8 if self.mp else 80 * self.n
         slot = self.ring.acquire(nbytes)
-        _lib.check(self.lib.x3d_particles_pack(b.h, self.h, slot.dev.data_ptr(), nbytes))
+        pack = self.lib.x3d_particles_mp_pack if self.mp else self.lib.x3d_particles_pack
+        _lib.check(pack(b.h, self.h, slot.dev.data_ptr(), nbytes))
         self.ring.submit(slot, nbytes, (int(it), float(it * self.solver.dt)))
         return True
 
     def _write_file(self, payload, raw):
         it, t = payload
-        out = unpack(raw, self.n)
+        if self.mp:  # `capacity` slots, then the local count and the flags: trimmed here
+            raw, cap = np.asarray(raw), self.capacity
+            n, flags = (int(v) for v in raw[80 * cap:80 * cap + 8].view(np.int32))
+            self._raise_flags(flags)
+            rows = raw[:72 * cap].view(np.float64).reshape(9, cap)[:, :n]
+            ints = raw[72 * cap:80 * cap].view(np.int32).reshape(2, cap)[:, :n]
+            out = unpack(np.concatenate([np.ascontiguousarray(rows).view(np.uint8).ravel(),
+                                         np.ascontiguousarray(ints).view(np.uint8).ravel()]), n, sorted_ids=True)
+        else:
+            out = unpack(raw, self.n)
         out["iteration"], out["time"] = np.int64(it), np.float64(t)
-        name = file_name(self.cfg.prefix, it)
+        name = file_name(self.cfg.prefix, it, self.rank if self.mp else None)
         with open(name, "wb") as fh:
             np.savez(fh, **out)
         self.files.append(name)
@@ -316,19 +489,53 @@ class Particles:
         return self.ring.waits
 
     # ------------------------------------------------------------ the state on the host
+    def _raise_flags(self, flags):
+        if flags:
+            raise X3dError("Particles: rank %d: %s" % (self.rank, "; ".join(text for bit, text in FLAGS if flags & bit)))
+
+    def check(self):
+        """one host wait: raises if this rank's migration ever overflowed or lost track of a particle; returns the local count"""
+        if not self.mp:
+            return self.n
+        q = _lib.ints(0, 0)
+        _lib.check(self.lib.x3d_particles_mp_query(self.solver.backend.h, self.h, q))
+        self._raise_flags(int(q[1]))
+        return int(q[0])
+
     def raw_state(self):
-        """(rows [12 or 18, n], id, status, has_history) in DEVICE order; one host wait"""
-        rows = np.empty((self.nrow, self.n), dtype=np.float64)
-        id_, status = np.empty(self.n, dtype=np.int32), np.empty(self.n, dtype=np.int32)
+        """(rows [12 or 18, n], id, status, has_history) in DEVICE order; one host wait.  Several ranks: this rank's own."""
+        n = self.capacity if self.mp else self.n
+        rows = np.empty((self.nrow, n), dtype=np.float64)
+        id_, status = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
         hist = ctypes.c_int(0)
-        _lib.check(self.lib.x3d_particles_download(self.solver.backend.h, self.h, rows.ctypes.data_as(DP),
-                                                   id_.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p),
-                                                   ctypes.byref(hist)))
-        return rows, id_, status, bool(hist.value)
+        args = (self.solver.backend.h, self.h, rows.ctypes.data_as(DP), id_.ctypes.data_as(_lib.c_int_p),
+                status.ctypes.data_as(_lib.c_int_p))
+        if not self.mp:
+            _lib.check(self.lib.x3d_particles_download(*args, ctypes.byref(hist)))
+            return rows, id_, status, bool(hist.value)
+        nl, flags = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(self.lib.x3d_particles_mp_download(*args, ctypes.byref(nl), ctypes.byref(flags), ctypes.byref(hist)))
+        self._raise_flags(flags.value)
+        nl = nl.value
+        return rows.ravel()[:self.nrow * nl].reshape(self.nrow, nl).copy(), id_[:nl].copy(), status[:nl].copy(), bool(hist.value)
+
+    def _gathered(self):
+        """(rows, id, status, has_history) of ALL ranks, rank after rank (collective; pickled bytes, so every bit survives)"""
+        rows, id_, status, hist = self.raw_state()
+        if not self.mp:
+            return rows, id_, status, hist
+        import torch.distributed as dist
+        parts = [None] * self.comm.size
+        dist.all_gather_object(parts, (rows, id_, status), group=self.comm.group)
+        rows, id_, status = (np.concatenate([q[k] for q in parts], axis=-1) for k in range(3))
+        if not np.array_equal(np.sort(id_), np.arange(self.n)):
+            raise X3dError("Particles.state: the ids over the ranks are not 0..n-1, each once")
+        return rows, id_, status, hist
 
     def state(self):
-        """id, x, v, a [n, 3], alive, status, iteration, time in id order: the only host wait"""
-        rows, id_, status, _ = self.raw_state()
+        """id, x, v, a [n, 3], alive, status, iteration, time in id order: the only host wait.  Several ranks: collective,
+        the global state on every rank."""
+        rows, id_, status, _ = self._gathered()
         rows, status = by_id(id_, rows, status)
         return {"id": np.arange(self.n, dtype=np.int64), "x": rows[0:3].T.copy(), "v": rows[3:6].T.copy(),
                 "a": rows[6:9].T.copy(), "alive": (status == 1).astype(np.int32), "status": status.astype(np.int32),
@@ -336,19 +543,30 @@ class Particles:
 
     def state_dict(self):
         """everything a resumed run needs, through the host in id order, under `particles_*` keys: 12 (tracers) or 18
-        (inertial) doubles and one int per particle"""
+        (inertial) doubles and one int per particle.  Several ranks: the rank's own particles and their `particles_id`."""
         rows, id_, status, hist = self.raw_state()
         rows, status = by_id(id_, rows, status)
-        return {"particles_n": np.int64(self.n), "particles_order": np.int64(self.cfg.order),
-                "particles_tau_p": np.float64(self.cfg.tau_p), "particles_iteration": np.int64(self.iteration),
-                "particles_has_history": np.bool_(hist), "particles_rows": rows, "particles_status": status.astype(np.int32)}
+        out = {"particles_n": np.int64(self.n), "particles_order": np.int64(self.cfg.order),
+               "particles_tau_p": np.float64(self.cfg.tau_p), "particles_iteration": np.int64(self.iteration),
+               "particles_has_history": np.bool_(hist), "particles_rows": rows, "particles_status": status.astype(np.int32)}
+        if self.mp:
+            out["particles_id"] = np.sort(id_).astype(np.int32)
+        return out
 
     def load_state_dict(self, z):
         check_state_dict(z, self.n, self.cfg.order, self.cfg.tau_p)
+        if self.mp != ("particles_id" in z):
+            raise X3dError("restore: the particles of the checkpoint belong to another decomposition")
         rows = np.ascontiguousarray(z["particles_rows"], dtype=np.float64)
         status = np.ascontiguousarray(z["particles_status"], dtype=np.int32)
-        id_ = np.arange(self.n, dtype=np.int32)
-        _lib.check(self.lib.x3d_particles_upload(self.solver.backend.h, self.h, rows.ctypes.data_as(DP),
-                                                 id_.ctypes.data_as(_lib.c_int_p), status.ctypes.data_as(_lib.c_int_p),
-                                                 int(bool(z["particles_has_history"]))))
+        b = self.solver.backend
+        if self.mp:  # (a particle this rank does not own is refused by the library: another rank's file)
+            id_ = np.ascontiguousarray(z["particles_id"], dtype=np.int32)
+            _lib.check(self.lib.x3d_particles_mp_upload(b.h, self.h, rows.ctypes.data_as(DP), id_.ctypes.data_as(_lib.c_int_p),
+                                                        status.ctypes.data_as(_lib.c_int_p), int(id_.size),
+                                                        int(bool(z["particles_has_history"]))))
+        else:
+            id_ = np.arange(self.n, dtype=np.int32)
+            _lib.check(self.lib.x3d_particles_upload(b.h, self.h, rows.ctypes.data_as(DP), id_.ctypes.data_as(_lib.c_int_p),
+                                                     status.ctypes.data_as(_lib.c_int_p), int(bool(z["particles_has_history"]))))
         self.iteration = int(z["particles_iteration"])
