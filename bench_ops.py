@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles|scalars]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles|scalars|forcing]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -95,6 +95,13 @@ streams); gate t_couple <= 1.15 t_vecadd; (b) x3d_scalars_couple at ns = 3 with 
 x3d_vecadd calls that compose the same terms; (c) x3d_scalars_profile_sums at ns = 1 next to x3d_stats_profile_sums; (d) 20
 fused RK3 TGV steps with one passive species against the same run with ri = 1: what giving up the deferred branch costs (wall
 time).  The lines are appended to profiles/scalars.jsonl.
+
+--family forcing (csrc/forcing.hip, x3d2_amd/forcing.py), at --snap-n (512) cubed on the velocity of make_hit, HIP events, the two
+sides of a comparison timed in turn inside one loop, median of --stat-iters with the quartiles: x3d_forcing_project next to
+x3d_stats_profile_sums on the same fields (both read u, v, w once) and x3d_forcing_synth next to three x3d_vecadd calls on the
+same blocks (x = y: the same bytes), at the default band (k_hi = 2.5: M = 2; gates 1.25 x) and at k_hi = 4.5 (M = 4: reported only); Forcing.add as a
+whole; 20 fused RK3 steps of make_hit without and with the forcing (wall time, no gate).  The lines are appended to
+profiles/forcing.jsonl.
 """
 import argparse
 import json
@@ -1384,13 +1391,97 @@ def bench_scalars(args):
           "added_ms_per_step": (res[1.0] - res[0.0]) / 20.0})
 
 
+def bench_forcing(args):
+    """one JSON line per measurement of the "forcing" family, printed and appended to profiles/forcing.jsonl"""
+    import ctypes
+
+    import torch
+    from x3d2_amd import _lib, make_hit
+    from x3d2_amd.common import DIR_X, VERT
+    from x3d2_amd.forcing import Forcing, ForcingConfig
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    out_path = os.path.join(ROOT, "profiles", "forcing.jsonl")
+
+    def emit(row):
+        row = dict({"family": "forcing", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    def alternating(fns):
+        """HIP-event ms of each fn in turn, --stat-iters rounds after --stat-warmup: both see the same machine state"""
+        ms, times = ctypes.c_float(), [[] for _ in fns]
+        for i in range(args.stat_warmup + args.stat_iters):
+            for k, fn in enumerate(fns):
+                _lib.check(b.lib.x3d_timer_start(b.h))
+                fn()
+                _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+                if i >= args.stat_warmup:
+                    times[k].append(ms.value)
+        return [spread(x) for x in times]
+
+    case = make_hit(n, fused=True)
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    d = [al.get_block(DIR_X, VERT) for _ in range(3)]
+    for f in d:
+        f.fill(0.0)
+    dof = float(n) ** 3
+    rate = lambda nbytes, t: {"bytes_per_dof": nbytes, "TBs": nbytes * dof / t["ms_median"] / 1e9,
+                              "ceiling": nbytes * dof / t["ms_median"] / 1e6 / 6200.0}
+    sums9 = torch.zeros(9 * n, dtype=_lib.torch_real(), device=b.device)
+    profile = lambda: b.stats_profile_sums(s.u, s.v, s.w, 2, sums9)
+
+    def three_vecadd():
+        for f in d:  # (x = y: one read and one write of each block, the bytes the synthesis moves)
+            b.vecadd(1e-3, f, 1.0, f)
+
+    for k_hi, gated in ((2.5, True), (4.5, False)):
+        frc = Forcing(s, ForcingConfig(scheme="power", power=0.1, k_hi=k_hi))
+        frc.add(d[0], d[1], d[2], s.u, s.v, s.w)  # (the coefficients the synthesis is timed with)
+        tag = "M = %d" % frc.M[0]
+        t_a, t_p = alternating([lambda: frc.project(s.u, s.v, s.w), profile])
+        emit(dict({"op": "x3d_forcing_project, %s (u, v, w read)" % tag, "row_pitch": b.padded_dims[0]}, **rate(3 * rb, t_a), **t_a))
+        emit(dict({"op": "x3d_stats_profile_sums, dir_keep = 2, on the same fields"}, **rate(3 * rb, t_p), **t_p))
+        t_c, t_v = alternating([lambda: frc.synthesise(d[0], d[1], d[2]), three_vecadd])
+        emit(dict({"op": "x3d_forcing_synth, %s (three derivative blocks read and written)" % tag}, **rate(6 * rb, t_c), **t_c))
+        emit(dict({"op": "three x3d_vecadd calls on the same blocks, x = y (three blocks read and written)"}, **rate(6 * rb, t_v), **t_v))
+        for name, t, y, what in (("t_A <= 1.25 t_profile_sums", t_a, t_p, "project"), ("t_C <= 1.25 t_3vecadd", t_c, t_v, "synth")):
+            row = {"op": ("gate: " if gated else "reported, no gate: ") + name + ", " + tag, what + "_ms_median": t["ms_median"],
+                   what + "_ms_q1_q3": [t["ms_q1"], t["ms_q3"]], "yardstick_ms_median": y["ms_median"],
+                   "yardstick_ms_q1_q3": [y["ms_q1"], y["ms_q3"]], "ratio": t["ms_median"] / y["ms_median"]}
+            if gated:
+                row.update(limit_ms=1.25 * y["ms_median"], passed=bool(t["ms_median"] <= 1.25 * y["ms_median"]))
+            emit(row)
+        t_add = spread(timed_events(args, b, lambda: frc.add(d[0], d[1], d[2], s.u, s.v, s.w)))
+        emit(dict({"op": "Forcing.add as a whole, %s" % tag, "row": frc.row()}, **t_add))
+        del frc
+    for f in d:
+        al.release_block(f)
+    # 20 fused RK3 steps without and with the forcing, on the same case
+    res = {}
+    for forced in (False, True):
+        s.forcing = Forcing(s, ForcingConfig(scheme="power", power=0.1, k_hi=2.5)) if forced else None
+        start = s.current_iter
+        case.run(n_iters=start + 3)
+        b.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=start + 23)
+        b.sync()
+        res[forced] = (time.perf_counter() - t0) * 1e3
+    emit({"op": "make_hit, fused, RK3: 20 steps without and with the band forcing (k_hi = 2.5)", "wall_ms_plain": res[False],
+          "wall_ms_forced": res[True], "ms_per_step_plain": res[False] / 20.0, "added_ms_per_step": (res[True] - res[False]) / 20.0,
+          "row": s.forcing.row()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "loads",
-                                                               "budgets", "les", "particles", "scalars"))
+                                                               "budgets", "les", "particles", "scalars", "forcing"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -1418,7 +1509,10 @@ def main():
         bench_particles(args)
     if args.family == "scalars":
         bench_scalars(args)
-    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les", "particles", "scalars"):
+    if args.family == "forcing":
+        bench_forcing(args)
+    if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les", "particles", "scalars",
+                       "forcing"):
         return
     import torch
     from x3d2_amd import Mesh

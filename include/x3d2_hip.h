@@ -1204,6 +1204,49 @@ int x3d_scalars_apply_bc(x3d_backend *b, x3d_real *const *phi, int ns, const int
 int x3d_scalars_profile_sums(x3d_backend *b, const x3d_real *u, const x3d_real *v, const x3d_real *w, const x3d_real *const *phi,
                              int ns, const int dims[3], int dir_keep, x3d_real *sums, x3d_real *minmax);
 
+/* ---- band forcing of a three-periodic box (csrc/forcing.hip).  Not in the reference: this project's own addition.
+ * The forced band lies in the mode box 0 <= mx <= M[0], |my| <= M[1], |mz| <= M[2] (the half space of a real field), mode index
+ * ((mx (2 M[1] + 1)) + my + M[1]) (2 M[2] + 1) + mz + M[2]; a coefficient array is [3][modes][re, im] doubles on the device, in
+ * both flavours.  U(m) = sum_x u(x) exp(-i k.x) is the unnormalised DFT (numpy's rfftn), k_d = 2 pi m_d / L_d.
+ *   x3d_forcing_project   uhat = U of u, v, w over this rank's block, by separable sums: one read of the three blocks.  The
+ *                         partial sums (`part`, part_cap doubles, at least sizes[2] of x3d_forcing_sizes) are formed in a fixed order
+ *                         and added by a small second launch in index order: no atomics, the launch geometry depends on the dims
+ *                         and the mode box alone, two calls on the same blocks give the same bits.  Several ranks: every rank
+ *                         projects its block (y and z may be cut, x never) and the caller adds the arrays over the ranks.
+ *   x3d_forcing_coeffs    one workgroup: g = uhat on the band (band[mode] != 0), with solenoidal != 0 minus its part along kvec[mode];
+ *                         D = sum w Re(g . conj U) / N^2 and E = 1/2 sum w |U|^2 / N^2 over the band, w = 1 for mx = 0, else 2, N the
+ *                         global number of points; fhat = c g with c = value / D (X3D_FORCING_POWER: the volume mean of f . u is then
+ *                         value) or c = value (X3D_FORCING_LINEAR), fhat = 0 and c = 0 where D <= d_min; row = {E, D, c, c D}.
+ *   x3d_forcing_synth     d_c(x) += (1 / N) sum_m w fhat_c(m) exp(i k.x) (real part: numpy's irfftn of the banded spectrum), one
+ *                         read-modify-write of the three blocks, the y / z part of the sum collapsed per plane and line, FP64 with
+ *                         one rounding at the store; nothing is written where row[X3D_FORCING_ROW_COEF] is 0.
+ * Tables (device, FP64 in both flavours, built by the host): tw_d[g][m] = {cos, -sin}(2 pi m g / n_d) for the GLOBAL point index
+ * g < nglobal[d] and m = 0 .. M[d].  Row padding is neither read into a result nor written.  No host wait; a queue of the
+ * deferred-execution layer runs first.  A bad argument (a null pointer, two blocks that are one, a direction that is not
+ * periodic, a cut x, a mode box beyond X3D_FORCING_MMAX or reaching the Nyquist mode, nband <= 0, a buffer too small) is an error
+ * and launches nothing. */
+#define X3D_FORCING_MMAX 8
+#define X3D_FORCING_NROW 4
+#define X3D_FORCING_ROW_COEF 2
+enum { X3D_FORCING_POWER = 0, X3D_FORCING_LINEAR = 1 };
+typedef struct x3d_forcing_params {
+    int nglobal[3], offset[3], nlocal[3]; /* vertex dims of the box, this rank's first point and dims */
+    int periodic[3];                      /* every one must be non-zero */
+    int M[3];                             /* the mode box */
+    int nband;                            /* modes with band[mode] != 0, as the host counted them */
+    const double *tw_x, *tw_y, *tw_z;     /* device twiddle tables */
+    const int *band;                      /* device, one flag per mode */
+    const double *kvec;                   /* device, [modes][3] wave vectors */
+} x3d_forcing_params;
+/* sizes = {modes, doubles of a coefficient array, doubles of the partial sums, doubles of the row} */
+int x3d_forcing_sizes(const x3d_forcing_params *params, long sizes[4]);
+int x3d_forcing_project(x3d_backend *b, const x3d_forcing_params *params, const x3d_real *u, const x3d_real *v, const x3d_real *w,
+                        double *part, long part_cap, double *uhat);
+int x3d_forcing_coeffs(x3d_backend *b, const x3d_forcing_params *params, const double *uhat, int scheme, double value,
+                       int solenoidal, double d_min, double *fhat, double *row);
+int x3d_forcing_synth(x3d_backend *b, const x3d_forcing_params *params, x3d_real *du, x3d_real *dv, x3d_real *dw, const double *fhat,
+                      const double *row);
+
 /* ---- measurement support: HIP-event timing on the backend's stream */
 int x3d_timer_start(x3d_backend *b);
 int x3d_timer_stop_ms(x3d_backend *b, float *ms);

@@ -25,6 +25,33 @@ def make_tgv(n, nproc_dir=(1, 1, 1), rank=0, Re=1600.0, dt=1e-3, time_intg="RK3"
     return TGVCase(solver)
 
 
+def make_hit(n, L=None, Re=1600.0, dt=1e-3, time_intg="RK3", k0=4.0, ke0=0.5, seed=0, forcing=None, fused=True,
+             nproc_dir=(1, 1, 1), rank=0, comm=None, poisson="FFT", device=None, lazy=None):
+    """homogeneous isotropic turbulence on an n^3 (or (nx, ny, nz)) three-periodic box L (default 2 pi each): an initial field
+    with E(k) ~ k^4 exp(-2 (k / k0)^2) and kinetic energy ke0 from default_rng(seed) (case.hit_initial_field), and, with
+    forcing = a forcing.ForcingConfig, the band forcing attached as solver.forcing.  y and z may be cut, x never.  Not in the
+    reference."""
+    from .backend import HipBackend
+    from .case import HITCase, HITConfig
+    from .solver import Solver, SolverConfig
+    dims = (n, n, n) if isinstance(n, int) else tuple(n)
+    twopi = 6.283185307179586
+    cfg = HITConfig(k0=k0, ke0=ke0, seed=seed)
+    if forcing is not None:
+        from .forcing import Forcing, ForcingConfig
+        if not isinstance(forcing, ForcingConfig):
+            raise X3dError("make_hit: forcing is a ForcingConfig or None")
+        if int(tuple(nproc_dir)[0]) > 1:
+            raise X3dError("make_hit: x is never cut (nproc_dir[0] = %d)" % int(tuple(nproc_dir)[0]))
+    mesh = Mesh(dims, tuple(nproc_dir), (twopi,) * 3 if L is None else tuple(L), ("periodic",) * 2, ("periodic",) * 2,
+                ("periodic",) * 2, nrank=rank)
+    backend = HipBackend(mesh, device=device, comm=comm, lazy=lazy)
+    solver = Solver(backend, mesh, SolverConfig(Re=Re, dt=dt, time_intg=time_intg, poisson_solver_type=poisson, fused=fused))
+    if forcing is not None:
+        solver.forcing = Forcing(solver, forcing)  # (refuses before the case generates its field)
+    return HITCase(solver, cfg)
+
+
 def make_channel(dims=(128, 65, 64), L=(4.0, 2.0, 2.0), stretching="top-bottom", beta=0.259065151, Re=4200.0,
                  dt=5e-3, time_intg="RK3", poisson="FFT", fused=False, device=None, comm=None, nproc_dir=(1, 1, 1),
                  rank=0, lazy=None, lowmem_transeq=False, n_species=0, pr_species=None, **channel_kw):

@@ -308,6 +308,10 @@ PROTOTYPES = {
     "x3d_scalars_couple": (I, [VP, ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), c_int_p, VP]),
     "x3d_scalars_apply_bc": (I, [VP, ctypes.POINTER(VP), I, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_double), I]),
     "x3d_scalars_profile_sums": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), I, c_int_p, I, VP, VP]),
+    "x3d_forcing_sizes": (I, [VP, ctypes.POINTER(ctypes.c_long)]),
+    "x3d_forcing_project": (I, [VP, VP, VP, VP, VP, VP, ctypes.c_long, VP]),
+    "x3d_forcing_coeffs": (I, [VP, VP, VP, I, ctypes.c_double, I, ctypes.c_double, VP, VP]),
+    "x3d_forcing_synth": (I, [VP, VP, VP, VP, VP, VP, VP]),
     "x3d_timer_start": (I, [VP]),
     "x3d_timer_stop_ms": (I, [VP, ctypes.POINTER(ctypes.c_float)]),
     "x3d_prof_enable": (I, [VP, I]),
@@ -338,6 +342,12 @@ class ScalarsParams(ctypes.Structure):
     """x3d_scalars_params of include/x3d2_hip.h"""
     _fields_ = [("ns", I), ("up", ctypes.c_double * 3), ("ri", ctypes.POINTER(ctypes.c_double)),
                 ("ref", ctypes.POINTER(ctypes.c_double)), ("grad", ctypes.POINTER(ctypes.c_double))]
+
+
+class ForcingParams(ctypes.Structure):
+    """x3d_forcing_params of include/x3d2_hip.h"""
+    _fields_ = [("nglobal", I * 3), ("offset", I * 3), ("nlocal", I * 3), ("periodic", I * 3), ("M", I * 3), ("nband", I),
+                ("tw_x", VP), ("tw_y", VP), ("tw_z", VP), ("band", VP), ("kvec", VP)]
 
 
 class ParticlesDecomp(ctypes.Structure):

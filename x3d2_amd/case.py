@@ -133,7 +133,8 @@ class BaseCase:
             walls, defer_upd = None, False
         les = s.les
         sca = s.scalars
-        if s.fused and les is None and self.forcings_idle(it) and (sca is None or not sca.coupled):
+        frc = s.forcing
+        if s.fused and les is None and frc is None and self.forcings_idle(it) and (sca is None or not sca.coupled):
             # nothing touches the derivatives between transeq and the RK / AB stage: the last accumulation of
             # transeq may be folded into the stage's linear combination (Solver.transeq_fused)
             pending = s.transeq(deriv, curr, defer=True)
@@ -143,6 +144,10 @@ class BaseCase:
         else:
             s.transeq(deriv, curr)
             self.forcings(deriv[0], deriv[1], deriv[2], it)
+            if frc is not None:
+                # the band forcing reads the velocity transeq has completed and needs the derivatives stored, like the subgrid term;
+                # its coefficients are those of THIS sub-step's velocity (forcing.Forcing: no state)
+                frc.add(deriv[0], deriv[1], deriv[2], s.u, s.v, s.w)
             if les is not None:
                 # the subgrid term reads the velocity transeq has completed (pending correction, bulk shift) and needs the
                 # derivatives stored: never the deferred branch above
@@ -293,6 +298,83 @@ class TGVCase(BaseCase):
         s.backend.set_field_data(s.u, np.sin(x) * np.cos(y) * np.cos(z))
         s.backend.set_field_data(s.v, -np.cos(x) * np.sin(y) * np.cos(z))
         s.w.fill(0.0)
+
+
+class HITConfig:
+    """k0: the peak of the initial spectrum E(k) ~ k^4 exp(-2 (k / k0)^2); ke0: the initial kinetic energy 1/2 <u.u>; seed: of
+    numpy's default_rng"""
+
+    def __init__(self, k0=4.0, ke0=0.5, seed=0):
+        self.k0, self.ke0, self.seed = float(k0), float(ke0), int(seed)
+        if not (self.k0 > 0.0 and self.ke0 > 0.0 and np.isfinite(self.k0) and np.isfinite(self.ke0)):
+            raise X3dError("HITConfig: k0 and ke0 are positive and finite")
+        if self.seed < 0:
+            raise X3dError("HITConfig: the seed must not be negative")
+
+
+def hit_initial_field(n, L, k0=4.0, ke0=0.5, seed=0):
+    """u, v, w [nz, ny, nx] on the GLOBAL three-periodic vertex grid n = (nx, ny, nz) of the box L, in float64 on the host: three
+    white-noise fields (default_rng(seed).standard_normal((nz, ny, nx)) for u, then v, then w), their rfftn times
+    |k| exp(-(|k| / k0)^2) (E(k) ~ k^4 exp(-2 (k / k0)^2), peak at k0), the Nyquist planes and the mean zeroed, the solenoidal
+    projection with the spectral k, the irfftn, and one scale factor so that 1/2 <u.u> = ke0"""
+    nx, ny, nz = (int(v) for v in n)
+    rng = np.random.default_rng(int(seed))
+    axes = (0, 1, 2)
+    hat = [np.fft.rfftn(rng.standard_normal((nz, ny, nx)), axes=axes) for _ in range(3)]
+    kz = (2.0 * np.pi / float(L[2])) * (np.fft.fftfreq(nz) * nz)[:, None, None]
+    ky = (2.0 * np.pi / float(L[1])) * (np.fft.fftfreq(ny) * ny)[None, :, None]
+    kx = (2.0 * np.pi / float(L[0])) * np.arange(nx // 2 + 1, dtype=np.float64)[None, None, :]
+    kk = kx * kx + ky * ky + kz * kz
+    k = np.sqrt(kk)
+    shape = k * np.exp(-(k / float(k0)) ** 2)
+    keep = np.ones(kk.shape)
+    keep[0, 0, 0] = 0.0
+    if nz % 2 == 0:
+        keep[nz // 2, :, :] = 0.0
+    if ny % 2 == 0:
+        keep[:, ny // 2, :] = 0.0
+    if nx % 2 == 0:
+        keep[:, :, nx // 2] = 0.0
+    hat = [h * shape * keep for h in hat]
+    kk_safe = np.where(kk > 0.0, kk, 1.0)
+    div = (kx * hat[0] + ky * hat[1] + kz * hat[2]) / kk_safe
+    hat = [hat[0] - kx * div, hat[1] - ky * div, hat[2] - kz * div]
+    f = [np.fft.irfftn(h, s=(nz, ny, nx), axes=axes) for h in hat]
+    ke = 0.5 * float(np.mean(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]))
+    if not ke > 0.0:
+        raise X3dError("hit_initial_field: the field is empty (k0 = %r on %r points)" % (k0, (nx, ny, nz)))
+    a = np.sqrt(float(ke0) / ke)
+    return [np.ascontiguousarray(a * x) for x in f]
+
+
+class HITCase(BaseCase):
+    """Homogeneous isotropic turbulence in a three-periodic box; not in the reference.  The initial field has a prescribed
+    spectrum (hit_initial_field, generated on the host from the GLOBAL grid, so that every rank slices the same field); with a
+    forcing.Forcing attached as solver.forcing (make_hit does it) the large scales are held and the flow becomes stationary."""
+
+    def __init__(self, solver, hit_cfg=None):
+        self.hit_cfg = hit_cfg or HITConfig()
+        super().__init__(solver)
+
+    def initial_conditions(self):
+        s, m, c = self.solver, self.solver.mesh, self.hit_cfg
+        if not all(m.periodic_BC) or any(m.stretched):
+            raise X3dError("HITCase: a three-periodic uniform box")
+        nx, ny, nz = (int(v) for v in m.get_dims(VERT))
+        ox, oy, oz = (int(o) for o in m.n_offset)
+        fields = hit_initial_field(m.get_global_dims(VERT), m.L, c.k0, c.ke0, c.seed)
+        for f, a in zip((s.u, s.v, s.w), fields):
+            f.set_data_loc(VERT)
+            s.backend.set_field_data(f, np.ascontiguousarray(a[oz:oz + nz, oy:oy + ny, ox:ox + nx]))
+
+    def checkpoint_state(self):
+        # (for the record only: the fields are in the checkpoint)
+        c = self.hit_cfg
+        return {"seed": np.uint64(c.seed), "k0": np.float64(c.k0), "ke0": np.float64(c.ke0)}
+
+    def load_checkpoint_state(self, state):
+        c = self.hit_cfg
+        c.seed, c.k0, c.ke0 = int(state["seed"]), float(state["k0"]), float(state["ke0"])
 
 
 class ChannelConfig:

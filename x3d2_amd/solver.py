@@ -164,6 +164,9 @@ class Solver:
         # optional scalars.Scalars(solver, cfg): BaseCase.substep then adds buoyancy and the imposed-gradient term to the
         # right-hand side and stamps the species' wall values; None = passive species as they were
         self.scalars = None
+        # optional forcing.Forcing(solver, cfg): BaseCase.substep then adds the band forcing to the right-hand side; None = no
+        # forcing, and the sub-step is what it was
+        self.forcing = None
         # keep_pressure / pressure (src/solver.f90:60-61, 705-714): the last pressure stays in a block of its own for the
         # snapshots (snapshot.Snapshots sets keep_pressure).  pressure_wanted: the fused driver keeps it only where the
         # case asks (BaseCase.step: the last sub-step of a step whose snapshot is due), see pressure_correction_fused
