@@ -6,7 +6,7 @@ n_iters timed launches.  Prints one JSON line per case: achieved GB/s on ALGORIT
 (tds_solve 16 B/DoF, transeq component 24 B/DoF, 16 when conv = u) and the reference's own convention
 (the "consumed bandwidth" its perf tests assume: 6 passes = 48 B for tds_solve, 16 passes = 128 B for transeq).
 
-    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles|scalars|forcing]
+    python bench_ops.py [--n 256,512,1024] [--iters 50] [--family all|operators|stats|ibm|snapshot|checkpoint|spectra|diagnostics|budgets|loads|les|particles|scalars|forcing|feedback]
 
 Family "statistics sample" (n^3 grids, n = 256 and 512; HIP-event time per launch group, median of --stat-iters after
 --stat-warmup): the fused 3-D update (x3d_stats_update_uvw, 168 B/DoF in FP64), the profile update along y
@@ -102,6 +102,13 @@ x3d_stats_profile_sums on the same fields (both read u, v, w once) and x3d_forci
 same blocks (x = y: the same bytes), at the default band (k_hi = 2.5: M = 2; gates 1.25 x) and at k_hi = 4.5 (M = 4: reported only); Forcing.add as a
 whole; 20 fused RK3 steps of make_hit without and with the forcing (wall time, no gate).  The lines are appended to
 profiles/forcing.jsonl.
+
+--family feedback (csrc/particles.hip x3d_particles_feedback_*, x3d2_amd/particles.py Feedback), at --snap-n (512) cubed with 2^20
+inertial particles from seed_uniform on the velocity of make_hit, HIP events, the two sides of a comparison timed in turn inside
+one loop, median of --stat-iters with the quartiles: Feedback.add (the eight passes) next to three x3d_vecadd calls on the same
+blocks (x = y; what a dense force field would cost per sub-step at the least: the gate, no margin); the record build (keys, two
+sorts, records) next to Particles.sort and x3d_particles_advance; the record build at 2^22 particles; 20 fused RK3 steps of
+make_hit with the particles one-way and two-way (wall time, no gate).  The lines are appended to profiles/feedback.jsonl.
 """
 import argparse
 import json
@@ -1475,13 +1482,103 @@ def bench_forcing(args):
           "row": s.forcing.row()})
 
 
+def bench_feedback(args):
+    """one JSON line per measurement of the "feedback" family, printed and appended to profiles/feedback.jsonl"""
+    import ctypes
+
+    from x3d2_amd import _lib, make_hit
+    from x3d2_amd.common import DIR_X, VERT
+    from x3d2_amd.particles import Particles, ParticlesConfig, mass_for_loading, seed_uniform
+    n, rb = args.snap_n, 4 if _lib.SINGLE else 8
+    out_path = os.path.join(ROOT, "profiles", "feedback.jsonl")
+
+    def emit(row):
+        row = dict({"family": "feedback", "n": n, "real_bytes": rb}, **row)
+        line = json.dumps(row)
+        print(line, flush=True)
+        with open(out_path, "a") as fh:
+            fh.write(line + "\n")
+
+    def alternating(fns):
+        """HIP-event ms of each fn in turn, --stat-iters rounds after --stat-warmup: both see the same machine state"""
+        ms, times = ctypes.c_float(), [[] for _ in fns]
+        for i in range(args.stat_warmup + args.stat_iters):
+            for k, fn in enumerate(fns):
+                _lib.check(b.lib.x3d_timer_start(b.h))
+                fn()
+                _lib.check(b.lib.x3d_timer_stop_ms(b.h, ctypes.byref(ms)))
+                if i >= args.stat_warmup:
+                    times[k].append(ms.value)
+        return [spread(x) for x in times]
+
+    case = make_hit(n, fused=True)
+    s = case.solver
+    b, al = s.backend, s.backend.allocator
+    tau = 20.0 * float(s.dt)
+
+    def particles(npart):
+        cfg = ParticlesConfig(seed_uniform(s.mesh, npart, seed=1), tau_p=tau, two_way=True, mass=mass_for_loading(s.mesh, npart, 0.2),
+                              v0=np.zeros((npart, 3)))
+        return Particles(s, cfg)
+
+    npart = 1 << 20
+    p = particles(npart)
+    fb = p.feedback
+    counts, _, _ = fb.records()
+    d = [al.get_block(DIR_X, VERT) for _ in range(3)]
+    for f in d:
+        f.fill(0.0)
+
+    def three_vecadd():
+        for f in d:  # (x = y: one read and one write of each block)
+            b.vecadd(1e-3, f, 1.0, f)
+
+    t_add, t_v = alternating([lambda: fb.add(d[0], d[1], d[2]), three_vecadd])
+    emit(dict({"op": "Feedback.add, eight passes, 2^20 particles", "particles": npart, "occupied_cells": int(counts[8]),
+               "cells_by_colour": [int(counts[c + 1] - counts[c]) for c in range(8)]}, **t_add))
+    emit(dict({"op": "three x3d_vecadd calls on the same blocks, x = y"}, **t_v))
+    emit({"op": "gate: t_add <= t_3vecadd", "add_ms_median": t_add["ms_median"], "add_ms_q1_q3": [t_add["ms_q1"], t_add["ms_q3"]],
+          "yardstick_ms_median": t_v["ms_median"], "yardstick_ms_q1_q3": [t_v["ms_q1"], t_v["ms_q3"]],
+          "ratio": t_add["ms_median"] / t_v["ms_median"], "passed": bool(t_add["ms_median"] <= t_v["ms_median"])})
+    for f in d:
+        al.release_block(f)
+    t_b, t_s, t_a = alternating([fb.build, p.sort, lambda: p.advance(s.u, s.v, s.w, 1e-9)])  # (dt tiny: the particles stay)
+    emit(dict({"op": "record build (keys, sort, marks, sort, offsets, records), 2^20 particles", "particles": npart}, **t_b))
+    emit(dict({"op": "Particles.sort, on the same state"}, **t_s))
+    emit(dict({"op": "x3d_particles_advance, order 4, on the same state"}, **t_a))
+    s.particle_feedback = None
+    del p, fb
+    big = particles(1 << 22)
+    (t_b4,) = alternating([big.feedback.build])
+    emit(dict({"op": "record build, 2^22 particles", "particles": 1 << 22, "occupied_cells": int(big.feedback.records()[0][8])}, **t_b4))
+    s.particle_feedback = None
+    del big
+    # 20 fused RK3 steps with the particles one-way and two-way, each on a case of its own
+    res = {}
+    del case, s, b, al
+    for two_way in (False, True):
+        case = make_hit(n, fused=True)
+        s = case.solver
+        extra = dict(two_way=True, mass=mass_for_loading(s.mesh, npart, 0.2)) if two_way else {}
+        case.particles = Particles(s, ParticlesConfig(seed_uniform(s.mesh, npart, seed=1), tau_p=tau, v0=np.zeros((npart, 3)), **extra))
+        case.run(n_iters=3)
+        s.backend.sync()
+        t0 = time.perf_counter()
+        case.run(n_iters=23)
+        s.backend.sync()
+        res[two_way] = (time.perf_counter() - t0) * 1e3
+        del case, s
+    emit({"op": "make_hit, fused, RK3: 20 steps with 2^20 inertial particles, one-way and two-way", "wall_ms_one_way": res[False],
+          "wall_ms_two_way": res[True], "ms_per_step_one_way": res[False] / 20.0, "added_ms_per_step": (res[True] - res[False]) / 20.0})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default="256,512,1024")  # the sizes of perf_cuda_tridiag
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--family", default="all", choices=("all", "operators", "stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "loads",
-                                                               "budgets", "les", "particles", "scalars", "forcing"))
+                                                               "budgets", "les", "particles", "scalars", "forcing", "feedback"))
     ap.add_argument("--snap-n", type=int, default=512)
     ap.add_argument("--stat-iters", type=int, default=30)
     ap.add_argument("--stat-warmup", type=int, default=5)
@@ -1511,8 +1608,10 @@ def main():
         bench_scalars(args)
     if args.family == "forcing":
         bench_forcing(args)
+    if args.family == "feedback":
+        bench_feedback(args)
     if args.family in ("stats", "ibm", "snapshot", "checkpoint", "spectra", "diagnostics", "budgets", "loads", "les", "particles", "scalars",
-                       "forcing"):
+                       "forcing", "feedback"):
         return
     import torch
     from x3d2_amd import Mesh

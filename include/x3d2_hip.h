@@ -1091,6 +1091,35 @@ int x3d_particles_pack(x3d_backend *b, const x3d_particles *p, void *dst_dev, lo
 int x3d_particles_download(x3d_backend *b, const x3d_particles *p, double *rows, int *id, int *status, int *has_history);
 int x3d_particles_upload(x3d_backend *b, x3d_particles *p, const double *rows, const int *id, const int *status, int has_history);
 
+/* ---- two-way coupling: the drag reaction of inertial particles on the fluid (csrc/particles.hip).  Not in the reference.
+ * One rank.  For every particle with status 1 the drag per unit fluid density is D = mass (a - v) / tau, component by
+ * component (no gravity); the fluid receives -D, spread with the TRILINEAR weights of the particle's cell (i, j, k) (the cell
+ * rule of the interpolation, whatever its order: w_1 = (x - c[i]) / (c[i + 1] - c[i]) with the periodic image of c[0] at L,
+ * w_0 = 1 - w_1) and divided by the dual volume of the vertex, whose three factors 1 / d the caller hands in.
+ *   enable  takes the storage (below) and the three host tables inv_d[n_d] of 1 / d; refuses tracers, a mass that is not
+ *           positive and finite, a periodic direction with an odd vertex count, particles on several ranks.
+ *   build   one key launch (cell 2^24 + id, 64 bits; particles that are not alive last), rocPRIM's radix_sort_pairs of (key, slot),
+ *           one launch that marks the first particle of every occupied cell with the cell's colour
+ *           (i mod 2) + 2 (j mod 2) + 4 (k mod 2), a second radix_sort_pairs on that 4-bit mark (stable: the occupied cells by
+ *           colour, then by cell), one small launch for the nine colour offsets, one launch that forms a record of 24 doubles
+ *           per occupied cell: for corner (alpha, beta, gamma) and component c the sum of wx_alpha wy_beta wz_gamma D_c over the
+ *           cell's particles IN ASCENDING ID, one lane per (corner, component).  The state is not reordered.
+ *   add     eight launches, colour 0 to 7: within a colour no two cells share a vertex, so each occupied cell does plain
+ *           read-modify-writes of its 8 vertices in the three blocks, d[vertex] += -R inv_dx inv_dy inv_dz, in FP64 with one
+ *           rounding at the store.  The cost follows the occupied cells, not the grid; row padding is neither read nor written.
+ * FP64 accumulation in both flavours, no atomics of any kind: the records depend on the (cell, id) order alone, so the same
+ * particles in any slot order give the same bits.  Storage taken by enable: 24 n bytes of keys and slots, 16 n of marks and
+ * positions, 4 n of cell indices, 192 n of records (n cells at most), rocPRIM's temporary storage.  No host wait except download.
+ * A bad argument (null, another backend's handle, two blocks that are one, dims other than the particles', add before build) is
+ * an error and launches nothing. */
+int x3d_particles_feedback_enable(x3d_backend *b, x3d_particles *p, double mass, const double *inv_dx, const double *inv_dy,
+                                  const double *inv_dz);
+int x3d_particles_feedback_build(x3d_backend *b, x3d_particles *p);
+int x3d_particles_feedback_add(x3d_backend *b, x3d_particles *p, x3d_real *du, x3d_real *dv, x3d_real *dw, const int dims[3]);
+/* counts[9] = the colour offsets (counts[8]: the occupied cells); cells[n] (or NULL) the cell index and records[24 n] (or NULL)
+ * the record of each occupied cell, in the order of the colour lists; waits for the stream.  For tests and measurements. */
+int x3d_particles_feedback_download(x3d_backend *b, const x3d_particles *p, int counts[9], unsigned *cells, double *records);
+
 /* ---- particles on several ranks (csrc/particles.hip).  Not in the reference.  y and z may be cut, x never is.  A rank holds
  * the particles it OWNS: rank r of a cut direction owns c[r nl] <= x < c[(r + 1) nl] on the GLOBAL table c, the last rank up to
  * L (periodic) or up to and including the last vertex; a particle of status 2 stays where it died.  The state is `capacity`

@@ -305,6 +305,10 @@ PROTOTYPES = {
     "x3d_particles_mp_pack": (I, [VP, VP, VP, ctypes.c_long]),
     "x3d_particles_mp_download": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]),
     "x3d_particles_mp_upload": (I, [VP, VP, ctypes.POINTER(ctypes.c_double), c_int_p, c_int_p, I, I]),
+    "x3d_particles_feedback_enable": (I, [VP, VP, ctypes.c_double] + [ctypes.POINTER(ctypes.c_double)] * 3),
+    "x3d_particles_feedback_build": (I, [VP, VP]),
+    "x3d_particles_feedback_add": (I, [VP, VP, VP, VP, VP, c_int_p]),
+    "x3d_particles_feedback_download": (I, [VP, VP, c_int_p, VP, VP]),
     "x3d_scalars_couple": (I, [VP, ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), ctypes.POINTER(VP), c_int_p, VP]),
     "x3d_scalars_apply_bc": (I, [VP, ctypes.POINTER(VP), I, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_double), I]),
     "x3d_scalars_profile_sums": (I, [VP, VP, VP, VP, ctypes.POINTER(VP), I, c_int_p, I, VP, VP]),

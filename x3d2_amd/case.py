@@ -134,7 +134,8 @@ class BaseCase:
         les = s.les
         sca = s.scalars
         frc = s.forcing
-        if s.fused and les is None and frc is None and self.forcings_idle(it) and (sca is None or not sca.coupled):
+        fb = s.particle_feedback
+        if s.fused and les is None and frc is None and fb is None and self.forcings_idle(it) and (sca is None or not sca.coupled):
             # nothing touches the derivatives between transeq and the RK / AB stage: the last accumulation of
             # transeq may be folded into the stage's linear combination (Solver.transeq_fused)
             pending = s.transeq(deriv, curr, defer=True)
@@ -148,6 +149,10 @@ class BaseCase:
                 # the band forcing reads the velocity transeq has completed and needs the derivatives stored, like the subgrid term;
                 # its coefficients are those of THIS sub-step's velocity (forcing.Forcing: no state)
                 frc.add(deriv[0], deriv[1], deriv[2], s.u, s.v, s.w)
+            if fb is not None:
+                # the drag reaction of two-way coupled particles: the records of the last update, the same in every sub-step of
+                # the step (particles.Feedback); eight sparse passes over the stored derivatives
+                fb.add(deriv[0], deriv[1], deriv[2])
             if les is not None:
                 # the subgrid term reads the velocity transeq has completed (pending correction, bulk shift) and needs the
                 # derivatives stored: never the deferred branch above

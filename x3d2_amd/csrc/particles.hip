@@ -46,6 +46,7 @@ struct x3d_particles {
     unsigned end_bit; // bits of the largest key
     unsigned dead_key;
     struct PartMp *mp; // several ranks (below): null on one rank
+    struct PartFb *fb; // two-way coupling (at the end of this file): null until enabled
 };
 
 // ---------------------------------------------------------------- the rule of one direction
@@ -312,11 +313,13 @@ __global__ void __launch_bounds__(256) k_particles_pack(const double *__restrict
 
 // ---------------------------------------------------------------- host side
 static void part_mp_free(x3d_particles *p);
+static void part_fb_free(x3d_particles *p);
 
 static void part_free(x3d_particles *p)
 {
     if (!p) return;
     part_mp_free(p);
+    part_fb_free(p);
     if (p->tabs) hipFree(p->tabs);
     for (int s = 0; s < 2; s++) {
         if (p->d[s]) hipFree(p->d[s]);
@@ -1547,5 +1550,317 @@ extern "C" int x3d_particles_mp_upload(x3d_backend *b, x3d_particles *p, const d
     X3D_HIP(hipMemcpy(p->mp->cnt, words, sizeof(words), hipMemcpyHostToDevice));
     p->primed = 1;
     p->has_hist = has_hist != 0;
+    return 0;
+}
+
+// ================================================================ two-way coupling
+// The drag reaction of the inertial particles on the fluid, without atomics of any kind and with one fixed order of every sum.
+//   build  keys (cell 2^24 + id, 64 bits) -> radix sort of (key, slot) -> the first particle of every occupied cell marked with
+//          the cell's colour (i mod 2) + 2 (j mod 2) + 4 (k mod 2), every other position with 8 -> radix sort of (mark, position)
+//          on 4 bits: stable, so the occupied cells come out by colour and, within a colour, by cell -> the nine colour offsets
+//          -> one record of FB_NREC doubles per occupied cell, lane (corner, component) walking the cell's particles in key
+//          order, that is in ascending id.  The state is not reordered.
+//   add    colour after colour: within a colour no two cells share a vertex (even vertex counts in the periodic directions; a
+//          non-periodic direction's last cell is n - 2), so every lane does a plain read-modify-write of its vertex.
+// The number of occupied cells lives on the device; the launches are sized by n and loop over what the offsets say.
+#define FB_NREC 24    // 8 corners x 3 components; lane = 3 corner + component, corner = alpha + 2 beta + 4 gamma
+#define FB_KEY_ID 24  // bits of the id in a key
+#define FB_BLOCKS (X3D_NCU * 8)
+
+struct PartFb {
+    double mass;
+    double *inv;                // the three tables of 1 / d, one allocation
+    const double *inv_d[3];
+    unsigned long long *keys;   // [2][n]: keys in, sorted out
+    int *slots;                 // [2][n]: 0..n-1 in, the slots in key order out
+    unsigned *marks;            // [2][n]: colour marks in, sorted out
+    int *pos;                   // [2][n]: 0..n-1 in, the positions of the cells' first particles, by colour, out
+    unsigned *cells;            // [n]: the cell of each record
+    int *coff;                  // [9]: the first record of each colour; [8]: the occupied cells
+    double *rec;                // [n][FB_NREC]
+    void *tmp;
+    size_t tmp_bytes;
+    unsigned end_bit;
+    unsigned long long dead_cell;  // nx ny nz: the cell of a particle that is not alive
+    int built;
+};
+
+static void part_fb_free(x3d_particles *p)
+{
+    PartFb *f = p->fb;
+    if (!f) return;
+    void *all[] = {f->inv, f->keys, f->slots, f->marks, f->pos, f->cells, f->coff, f->rec, f->tmp};
+    for (void *q : all)
+        if (q) hipFree(q);
+    delete f;
+    p->fb = nullptr;
+}
+
+struct FbGrid {
+    int nx, ny, nz;
+    long nxp, nyp;
+    unsigned long long ncell;
+};
+
+__global__ void __launch_bounds__(256) k_fb_keys(PartGeom G, const double *__restrict__ d, const int *__restrict__ ints, int n,
+                                                 unsigned long long dead_cell, unsigned long long *__restrict__ keys,
+                                                 int *__restrict__ slots)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const long N = n;
+    unsigned long long cell = dead_cell;
+    if (ints[N + t] == 1) {  // (an alive particle's position is finite and inside: k_particles_advance)
+        const unsigned long long i = (unsigned)part_cell(G.ax[0], d[(P_X + 0) * N + t]);
+        const unsigned long long j = (unsigned)part_cell(G.ax[1], d[(P_X + 1) * N + t]);
+        const unsigned long long k = (unsigned)part_cell(G.ax[2], d[(P_X + 2) * N + t]);
+        cell = (k * (unsigned)G.ax[1].n + j) * (unsigned)G.ax[0].n + i;
+    }
+    keys[t] = (cell << FB_KEY_ID) | ((unsigned)ints[t] & ((1u << FB_KEY_ID) - 1u));
+    slots[t] = t;
+}
+
+__global__ void __launch_bounds__(256) k_fb_marks(FbGrid g, const unsigned long long *__restrict__ keys, int n,
+                                                  unsigned *__restrict__ marks, int *__restrict__ pos)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const unsigned long long cell = keys[t] >> FB_KEY_ID;
+    unsigned mark = 8u;
+    if (cell < g.ncell && (t == 0 || (keys[t - 1] >> FB_KEY_ID) != cell)) {
+        const unsigned i = (unsigned)(cell % (unsigned)g.nx), j = (unsigned)((cell / (unsigned)g.nx) % (unsigned)g.ny);
+        const unsigned k = (unsigned)(cell / ((unsigned long long)g.nx * (unsigned)g.ny));
+        mark = (i & 1u) + 2u * (j & 1u) + 4u * (k & 1u);
+    }
+    marks[t] = mark;
+    pos[t] = t;
+}
+
+// coff[c] = the number of sorted marks below c, c = 0 .. 8
+__global__ void __launch_bounds__(64) k_fb_offsets(const unsigned *__restrict__ marks, int n, int *__restrict__ coff)
+{
+    const unsigned c = threadIdx.x;
+    if (c > 8u) return;
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (marks[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    coff[c] = lo;
+}
+
+// w_1 of cell i of one direction
+__device__ __forceinline__ double fb_w1(const PartAxis &A, int i, double x)
+{
+    const double lo = A.c[i], hi = i + 1 < A.n ? A.c[i + 1] : A.L;  // (i + 1 == n only in a periodic direction: the image of c[0])
+    return (x - lo) / (hi - lo);
+}
+
+__global__ void __launch_bounds__(256) k_fb_records(PartGeom G, FbGrid g, const double *__restrict__ d,
+                                                    const unsigned long long *__restrict__ keys, const int *__restrict__ slots,
+                                                    const int *__restrict__ pos, const int *__restrict__ coff, int n, double mass,
+                                                    double tau, unsigned *__restrict__ cells, double *__restrict__ rec)
+{
+    const long N = n;
+    const long total = (long)min(max(coff[8], 0), n) * FB_NREC;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const long q = e / FB_NREC;
+        const int lane = (int)(e - q * FB_NREC), corner = lane / 3, comp = lane - 3 * corner;
+        int t = pos[q];
+        double sum = 0.0;
+        unsigned long long cell = g.ncell;
+        if (t >= 0 && t < n) cell = keys[t] >> FB_KEY_ID;
+        if (cell < g.ncell) {
+            const int i = (int)(cell % (unsigned)g.nx), j = (int)((cell / (unsigned)g.nx) % (unsigned)g.ny);
+            const int k = (int)(cell / ((unsigned long long)g.nx * (unsigned)g.ny));
+            for (; t < n && (keys[t] >> FB_KEY_ID) == cell; t++) {
+                const int s = slots[t];
+                if (s < 0 || s >= n) continue;  // (a permutation of 0..n-1; never an address from anything else)
+                const double w1x = fb_w1(G.ax[0], i, d[(P_X + 0) * N + s]);
+                const double w1y = fb_w1(G.ax[1], j, d[(P_X + 1) * N + s]);
+                const double w1z = fb_w1(G.ax[2], k, d[(P_X + 2) * N + s]);
+                const double wx = (corner & 1) ? w1x : 1.0 - w1x, wy = (corner & 2) ? w1y : 1.0 - w1y;
+                const double wz = (corner & 4) ? w1z : 1.0 - w1z;
+                const double D = mass * (d[(P_A + comp) * N + s] - d[(P_V + comp) * N + s]) / tau;
+                sum += ((wx * wy) * wz) * D;
+            }
+        }
+        rec[e] = sum;
+        if (lane == 0) cells[q] = (unsigned)cell;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_fb_apply(FbGrid g, int px, int py, int pz, int colour, const int *__restrict__ coff,
+                                                  const unsigned *__restrict__ cells, const double *__restrict__ rec,
+                                                  const double *__restrict__ invx, const double *__restrict__ invy,
+                                                  const double *__restrict__ invz, int ncap, real_t *du, real_t *dv, real_t *dw)
+{
+    const long lo = (long)min(max(coff[colour], 0), ncap) * FB_NREC, hi = (long)min(max(coff[colour + 1], 0), ncap) * FB_NREC;
+    for (long e = lo + (long)blockIdx.x * 256 + threadIdx.x; e < hi; e += (long)gridDim.x * 256) {
+        const long q = e / FB_NREC;
+        const int lane = (int)(e - q * FB_NREC), corner = lane / 3, comp = lane - 3 * corner;
+        const unsigned long long cell = cells[q];
+        if (cell >= g.ncell) continue;
+        int i = (int)(cell % (unsigned)g.nx) + (corner & 1), j = (int)((cell / (unsigned)g.nx) % (unsigned)g.ny) + ((corner >> 1) & 1);
+        int k = (int)(cell / ((unsigned long long)g.nx * (unsigned)g.ny)) + ((corner >> 2) & 1);
+        // node n of a periodic direction is node 0; a non-periodic direction's last cell is n - 2, so nothing else gets here
+        if (i >= g.nx) { if (!px) continue; i = 0; }
+        if (j >= g.ny) { if (!py) continue; j = 0; }
+        if (k >= g.nz) { if (!pz) continue; k = 0; }
+        const double val = -rec[e] * ((invx[i] * invy[j]) * invz[k]);
+        real_t *blk = comp == 0 ? du : (comp == 1 ? dv : dw);
+        const long off = i + g.nxp * ((long)j + g.nyp * (long)k);
+        blk[off] = (real_t)((double)blk[off] + val);
+    }
+}
+
+static FbGrid fb_grid(const x3d_particles *p)
+{
+    FbGrid g;
+    g.nx = p->G.ax[0].n; g.ny = p->G.ax[1].n; g.nz = p->G.ax[2].n;
+    g.nxp = p->G.nxp; g.nyp = p->G.nyp;
+    g.ncell = p->fb->dead_cell;
+    return g;
+}
+
+static unsigned fb_blocks(long lanes)
+{
+    const long want = (lanes + 255) / 256;
+    return (unsigned)(want > FB_BLOCKS ? FB_BLOCKS : (want < 1 ? 1 : want));
+}
+
+#define FB_ARGS(name)                                                                                                            \
+    X3D_REQUIRE(b && p, name ": null argument");                                                                                 \
+    X3D_REQUIRE(p->b == b, name ": the particles belong to another backend");                                                    \
+    X3D_REQUIRE(!p->mp, name ": two-way coupling is not built on several ranks")
+
+extern "C" int x3d_particles_feedback_enable(x3d_backend *b, x3d_particles *p, double mass, const double *inv_dx, const double *inv_dy,
+                                             const double *inv_dz)
+{
+    X3D_RANGE(__func__);
+    FB_ARGS("x3d_particles_feedback_enable");
+    X3D_REQUIRE(inv_dx && inv_dy && inv_dz, "x3d_particles_feedback_enable: null argument");
+    X3D_REQUIRE(!p->fb, "x3d_particles_feedback_enable: already enabled");
+    X3D_REQUIRE(p->inertial, "x3d_particles_feedback_enable: tracers (tau = 0) exert no drag");
+    X3D_REQUIRE(std::isfinite(mass) && mass > 0.0, "x3d_particles_feedback_enable: the mass must be positive and finite");
+    const double *tab[3] = {inv_dx, inv_dy, inv_dz};
+    size_t ntab = 0;
+    for (int c = 0; c < 3; c++) {
+        const PartAxis &A = p->G.ax[c];
+        X3D_REQUIRE(!A.periodic || A.n % 2 == 0,
+                    "x3d_particles_feedback_enable: periodic direction %d has %d vertices, the cell colouring needs an even count", c + 1, A.n);
+        for (int i = 0; i < A.n; i++)
+            X3D_REQUIRE(std::isfinite(tab[c][i]) && tab[c][i] > 0.0, "x3d_particles_feedback_enable: 1 / d of direction %d is not positive and finite",
+                        c + 1);
+        ntab += (size_t)A.n;
+    }
+    // ---- nothing was allocated up to here
+    PartFb *f = new PartFb();
+    p->fb = f;
+    f->mass = mass;
+    f->dead_cell = (unsigned long long)p->G.ax[0].n * (unsigned long long)p->G.ax[1].n * (unsigned long long)p->G.ax[2].n;
+    f->end_bit = FB_KEY_ID + 1;
+    while (f->end_bit < 64 && (f->dead_cell >> (f->end_bit - FB_KEY_ID)) != 0) f->end_bit++;
+    const size_t n = (size_t)p->n;
+    hipError_t e = hipSuccess;
+    auto alloc = [&e](void **q, size_t bytes) { if (e == hipSuccess) e = hipMalloc(q, bytes); };
+    alloc(reinterpret_cast<void **>(&f->inv), sizeof(double) * ntab);
+    alloc(reinterpret_cast<void **>(&f->keys), sizeof(unsigned long long) * 2 * n);
+    alloc(reinterpret_cast<void **>(&f->slots), sizeof(int) * 2 * n);
+    alloc(reinterpret_cast<void **>(&f->marks), sizeof(unsigned) * 2 * n);
+    alloc(reinterpret_cast<void **>(&f->pos), sizeof(int) * 2 * n);
+    alloc(reinterpret_cast<void **>(&f->cells), sizeof(unsigned) * n);
+    alloc(reinterpret_cast<void **>(&f->coff), sizeof(int) * 9);
+    alloc(reinterpret_cast<void **>(&f->rec), sizeof(double) * FB_NREC * n);
+    size_t b1 = 0, b2 = 0;
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(nullptr, b1, f->keys, f->keys + n, f->slots, f->slots + n, (unsigned)n, 0u, f->end_bit, b->stream);
+    if (e == hipSuccess)
+        e = rocprim::radix_sort_pairs(nullptr, b2, f->marks, f->marks + n, f->pos, f->pos + n, (unsigned)n, 0u, 4u, b->stream);
+    f->tmp_bytes = std::max<size_t>(std::max(b1, b2), 16);
+    alloc(&f->tmp, f->tmp_bytes);
+    size_t off = 0;
+    for (int c = 0; c < 3 && e == hipSuccess; c++) {  // (the caller's tables may die with this call: synchronous copies)
+        e = hipMemcpy(f->inv + off, tab[c], sizeof(double) * p->G.ax[c].n, hipMemcpyHostToDevice);
+        f->inv_d[c] = f->inv + off;
+        off += (size_t)p->G.ax[c].n;
+    }
+    if (e == hipSuccess) e = hipMemset(f->coff, 0, sizeof(int) * 9);
+    if (e != hipSuccess) {
+        part_fb_free(p);
+        x3d_set_error("x3d_particles_feedback_enable: %s", hipGetErrorString(e));
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int x3d_particles_feedback_build(x3d_backend *b, x3d_particles *p)
+{
+    X3D_RANGE(__func__);
+    FB_ARGS("x3d_particles_feedback_build");
+    X3D_REQUIRE(p->fb, "x3d_particles_feedback_build: two-way coupling was not enabled");
+    X3D_REQUIRE(p->primed, "x3d_particles_feedback_build: the state was neither primed nor loaded");
+    PartFb *f = p->fb;
+    const int n = p->n, cur = p->cur;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    const FbGrid g = fb_grid(p);
+    ProfScope ps(b, X3D_K_COPY);
+    hipLaunchKernelGGL(k_fb_keys, grid, dim3(256), 0, b->stream, p->G, (const double *)p->d[cur], (const int *)p->ints[cur], n, f->dead_cell,
+                       f->keys, f->slots);
+    X3D_HIP(hipGetLastError());
+    size_t bytes = f->tmp_bytes;
+    X3D_HIP(rocprim::radix_sort_pairs(f->tmp, bytes, f->keys, f->keys + n, f->slots, f->slots + n, (unsigned)n, 0u, f->end_bit, b->stream));
+    hipLaunchKernelGGL(k_fb_marks, grid, dim3(256), 0, b->stream, g, (const unsigned long long *)(f->keys + n), n, f->marks, f->pos);
+    X3D_HIP(hipGetLastError());
+    bytes = f->tmp_bytes;
+    X3D_HIP(rocprim::radix_sort_pairs(f->tmp, bytes, f->marks, f->marks + n, f->pos, f->pos + n, (unsigned)n, 0u, 4u, b->stream));
+    hipLaunchKernelGGL(k_fb_offsets, dim3(1), dim3(64), 0, b->stream, (const unsigned *)(f->marks + n), n, f->coff);
+    hipLaunchKernelGGL(k_fb_records, dim3(fb_blocks((long)n * FB_NREC)), dim3(256), 0, b->stream, p->G, g, (const double *)p->d[cur],
+                       (const unsigned long long *)(f->keys + n), (const int *)(f->slots + n), (const int *)(f->pos + n),
+                       (const int *)f->coff, n, f->mass, p->tau, f->cells, f->rec);
+    X3D_HIP(hipGetLastError());
+    f->built = 1;
+    return 0;
+}
+
+extern "C" int x3d_particles_feedback_add(x3d_backend *b, x3d_particles *p, real_t *du, real_t *dv, real_t *dw, const int dims[3])
+{
+    X3D_RANGE(__func__);
+    FB_ARGS("x3d_particles_feedback_add");
+    X3D_REQUIRE(du && dv && dw && dims, "x3d_particles_feedback_add: null argument");
+    X3D_REQUIRE(du != dv && du != dw && dv != dw, "x3d_particles_feedback_add: two derivative blocks are the same block");
+    X3D_REQUIRE(p->fb && p->fb->built, "x3d_particles_feedback_add: the records were not built");
+    X3D_REQUIRE(dims[0] == p->G.ax[0].n && dims[1] == p->G.ax[1].n && dims[2] == p->G.ax[2].n && dims[0] <= b->nxp && dims[1] <= b->nyp &&
+                    dims[2] <= b->nzp,
+                "x3d_particles_feedback_add: dims (%d,%d,%d) are not the vertices the particles were created for", dims[0], dims[1], dims[2]);
+    X3D_LAZY_OUT(b, du, false);
+    X3D_LAZY_OUT(b, dv, false);
+    X3D_LAZY_OUT(b, dw, false);
+    X3D_LAZY_EAGER(b);
+    const PartFb *f = p->fb;
+    const FbGrid g = fb_grid(p);
+    // (the lists of the eight colours share the occupied cells: an eighth of the lanes each, on average)
+    const unsigned blocks = fb_blocks(((long)p->n * FB_NREC + 7) / 8);
+    ProfScope ps(b, X3D_K_BLAS1);
+    for (int colour = 0; colour < 8; colour++)
+        hipLaunchKernelGGL(k_fb_apply, dim3(blocks), dim3(256), 0, b->stream, g, p->G.ax[0].periodic, p->G.ax[1].periodic, p->G.ax[2].periodic,
+                           colour, (const int *)f->coff, (const unsigned *)f->cells, (const double *)f->rec, f->inv_d[0], f->inv_d[1],
+                           f->inv_d[2], p->n, du, dv, dw);
+    X3D_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int x3d_particles_feedback_download(x3d_backend *b, const x3d_particles *p, int counts[9], unsigned *cells, double *records)
+{
+    X3D_RANGE(__func__);
+    FB_ARGS("x3d_particles_feedback_download");
+    X3D_REQUIRE(counts, "x3d_particles_feedback_download: null argument");
+    X3D_REQUIRE(p->fb && p->fb->built, "x3d_particles_feedback_download: the records were not built");
+    X3D_HIP(hipStreamSynchronize(b->stream));
+    b->n_sync++;
+    X3D_HIP(hipMemcpy(counts, p->fb->coff, sizeof(int) * 9, hipMemcpyDeviceToHost));
+    const size_t nc = (size_t)std::min(std::max(counts[8], 0), p->n);
+    if (cells && nc) X3D_HIP(hipMemcpy(cells, p->fb->cells, sizeof(unsigned) * nc, hipMemcpyDeviceToHost));
+    if (records && nc) X3D_HIP(hipMemcpy(records, p->fb->rec, sizeof(double) * FB_NREC * nc, hipMemcpyDeviceToHost));
     return 0;
 }

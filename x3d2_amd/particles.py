@@ -54,7 +54,17 @@ with no host wait of its own (a host-staged transport waits in sendrecv).  The s
 More leavers than mig_capacity, more residents than capacity, or a particle owned neither here nor by a ring neighbour set a
 sticky device flag and keep the particle where it is; state(), raw_state(), state_dict(), check() and the file writer raise an
 X3dError that names the cause and the rank.  state() is collective and returns the global state on every rank; files are
-`<prefix>_<it:06d>.r<rank>.npz`, which load_particles assembles; interpolate is refused."""
+`<prefix>_<it:06d>.r<rank>.npz`, which load_particles assembles; interpolate is refused.
+
+Two-way coupling (ParticlesConfig(tau_p > 0, two_way=True, mass=m), one rank): the fluid receives the drag reaction
+-D_p = -mass (a_p - v_p) / tau_p of every alive particle (no gravity; mass = particle mass / fluid density) through the TRILINEAR
+weights of the particle's cell, whatever `order` interpolates, each vertex share divided by the vertex's dual volume
+dx_i dy_j dz_k (dual_widths), so that sum f V = -sum D_p.  Particles then sets solver.particle_feedback = Feedback (below):
+build() at the end of every update (and at priming and after a restore) forms one record of 24 doubles per occupied cell, each
+summed in ascending id; BaseCase.substep adds them to the derivatives of every sub-step of the next step, after the band forcing
+and before the subgrid term, in eight passes by cell colour.  No atomics, one order of every sum: the same particles in any slot
+order give the same bits.  Refused before anything is allocated: tau_p = 0, a mass that is missing, not positive or not finite,
+a periodic direction with an odd vertex count, several ranks."""
 import ctypes
 import glob
 import math
@@ -81,10 +91,22 @@ class ParticlesConfig:
     inertial particles (None: the fluid's); wall: "reflect" or "absorb"; advance from iteration initpart on (<= 0: never);
     a file every ipartout iterations (0: none); sort by cell every sort_every iterations (0: never; 8 is the measured
     minimum of advance plus amortised sort, README); several ranks: capacity slots of state per rank (None:
-    ceil(1.5 n / nproc) + 1024) and mig_capacity slots per migration message (None: max(1024, capacity // 8))"""
+    ceil(1.5 n / nproc) + 1024) and mig_capacity slots per migration message (None: max(1024, capacity // 8)); two_way: the
+    drag reaction acts on the fluid (inertial particles on one rank), with mass = one positive finite number, a particle's
+    mass divided by the fluid density (mass_for_loading gives it from a mass loading)"""
 
     def __init__(self, x0, order=4, tau_p=0.0, gravity=(0.0, 0.0, 0.0), v0=None, wall="reflect", initpart=1, ipartout=0,
-                 prefix="particles", sort_every=8, capacity=None, mig_capacity=None):
+                 prefix="particles", sort_every=8, capacity=None, mig_capacity=None, two_way=False, mass=None):
+        self.two_way = bool(two_way)
+        self.mass = None
+        if self.two_way:  # (refused before anything else is looked at: nothing of a refused config exists)
+            if not float(tau_p) > 0.0:
+                raise X3dError("ParticlesConfig: two_way needs inertial particles (tau_p > 0): a tracer exerts no drag")
+            if mass is None or isinstance(mass, (str, bytes, bool)) or not isinstance(mass, (int, float, np.integer, np.floating)) \
+                    or not math.isfinite(float(mass)) or not float(mass) > 0.0:
+                raise X3dError("ParticlesConfig: two_way needs mass, one positive finite number: a particle's mass divided by "
+                               "the fluid density (got %r)" % (mass,))
+            self.mass = float(mass)
         x = np.array(x0, dtype=np.float64)
         if x.ndim != 2 or x.shape[1] != 3 or not 1 <= x.shape[0] <= MAX_PARTICLES:
             raise X3dError("ParticlesConfig: x0 is an [n, 3] array of positions, 1 <= n <= %d" % MAX_PARTICLES)
@@ -146,6 +168,40 @@ class ParticlesConfig:
 def ab2_coefficients(first):
     """(c1, c0) of x += dt (c1 v + c0 v_prev): explicit Euler on the first advance after priming, AB2 afterwards"""
     return (1.0, 0.0) if first else (1.5, -0.5)
+
+
+def mass_for_loading(mesh, n, phi):
+    """the `mass` of ParticlesConfig at which n particles carry the mass loading phi (particle mass over fluid mass in the
+    box): phi Lx Ly Lz / n"""
+    n, phi = int(n), float(phi)
+    if n < 1 or not math.isfinite(phi) or not phi > 0.0:
+        raise X3dError("mass_for_loading: n >= 1 particles and a positive finite loading")
+    return phi * float(mesh.L[0]) * float(mesh.L[1]) * float(mesh.L[2]) / n
+
+
+def dual_widths(c, periodic, L):
+    """d_i of the vertices c of one direction, the factors of a vertex's dual volume: L / n in a periodic (uniform) direction;
+    otherwise half the first and the last spacing at the ends and (c[i + 1] - c[i - 1]) / 2 between them"""
+    c = np.asarray(c, dtype=np.float64)
+    n = c.size
+    if periodic:
+        return np.full(n, float(L) / n)
+    d = np.empty(n)
+    d[0], d[-1] = 0.5 * (c[1] - c[0]), 0.5 * (c[-1] - c[-2])
+    d[1:-1] = 0.5 * (c[2:] - c[:-2])
+    return d
+
+
+def check_two_way(mesh, comm_size):
+    """X3dError for a mesh or a communicator the two-way coupling does not serve"""
+    if int(mesh.nproc) != 1 or int(comm_size) != 1:
+        raise X3dError("Particles: two_way is not built on several ranks (the mesh has %d, the communicator %d)"
+                       % (int(mesh.nproc), int(comm_size)))
+    for d in range(3):
+        n = int(mesh.global_vert_dims[d])
+        if mesh.periodic_BC[d] and n % 2:
+            raise X3dError("Particles: two_way needs an even vertex count in a periodic direction (the cell colouring), "
+                           "direction %d has %d" % (d + 1, n))
 
 
 def seed_uniform(mesh, n, seed=0):
@@ -252,8 +308,11 @@ class Particles:
     write(it) and poll() once per step and finalise() at the end; checkpoint.Checkpoints carries state_dict()."""
 
     def __init__(self, solver, cfg):
+        self.h, self.feedback = None, None  # (a refusal below leaves both)
         self.solver, self.cfg = solver, cfg
         b, m = solver.backend, solver.mesh
+        if cfg.two_way:
+            check_two_way(m, int(getattr(b.comm, "size", 1)))
         self.mp = int(m.nproc) != 1
         self.rank, self.comm = int(m.nrank), b.comm
         self.n, self.nrow = cfg.n, 18 if cfg.inertial else 12
@@ -291,7 +350,20 @@ class Particles:
         self.ring = CopyRing(b, 2, self._write_file)  # (nothing is allocated until the first write)
         self.files = []
         self.iteration = int(solver.current_iter)  # the iteration the state belongs to
+        if cfg.two_way:
+            self.feedback = Feedback(self)
         self.prime()
+        if cfg.two_way:
+            self._records()
+            solver.particle_feedback = self.feedback
+
+    def _records(self):
+        """two-way coupling: the records of the state as it is, from iteration initpart - 1 on; before that the particles
+        rest and nothing is added"""
+        if self.reads_state(self.iteration):
+            self.feedback.build()
+        else:
+            self.feedback.built = False
 
     def owned(self, x):
         """which of the (wrapped) positions x [m, 3] this rank owns"""
@@ -441,6 +513,8 @@ class Particles:
         elif self.reads_state(it):
             self.prime()  # it == initpart - 1, resting until now: the history starts here
         self.iteration = it  # (only once the launches were accepted: a refused advance leaves the count with the state)
+        if self.feedback is not None:
+            self._records()  # applied unchanged in every sub-step of step it + 1
         return moved
 
     def write(self, it):
@@ -570,3 +644,59 @@ class Particles:
             _lib.check(self.lib.x3d_particles_upload(b.h, self.h, rows.ctypes.data_as(DP), id_.ctypes.data_as(_lib.c_int_p),
                                                      status.ctypes.data_as(_lib.c_int_p), int(bool(z["particles_has_history"]))))
         self.iteration = int(z["particles_iteration"])
+        if self.feedback is not None:
+            self._records()  # from the restored x, v, a: the records are no state of their own
+
+
+class Feedback:
+    """The drag reaction of two-way coupled particles on the fluid, Particles.feedback and solver.particle_feedback
+    (csrc/particles.hip, x3d_particles_feedback_*).  build() forms the records of the occupied cells from the particle state as
+    it is (Particles does it at the end of every update, at priming and after a restore); add(du, dv, dw) applies them to three
+    derivative blocks in eight passes by cell colour (BaseCase.substep, after the band forcing and before the subgrid term);
+    before the first build nothing is added.  No call waits for the host except field() readers and records()."""
+
+    coupled = True  # the derivatives must be stored: BaseCase.substep's explicit branch
+
+    def __init__(self, particles):
+        p = self.particles = particles
+        m, b = p.solver.mesh, p.solver.backend
+        self.lib, self.mass, self.built = b.lib, float(p.cfg.mass), False
+        self.inv_d = [np.ascontiguousarray(1.0 / dual_widths(p.coords[d], bool(m.periodic_BC[d]), float(m.L[d]))) for d in range(3)]
+        _lib.check(self.lib.x3d_particles_feedback_enable(b.h, p.h, self.mass, *(t.ctypes.data_as(DP) for t in self.inv_d)))
+
+    def build(self):
+        """keys, sort, records of the state as it is; no host wait"""
+        p = self.particles
+        _lib.check(self.lib.x3d_particles_feedback_build(p.solver.backend.h, p.h))
+        self.built = True
+
+    def add(self, du, dv, dw):
+        """du, dv, dw += f of the records; no host wait"""
+        if not self.built:
+            return
+        p = self.particles
+        b = p.solver.backend
+        for f in (du, dv, dw):
+            if f.dir != DIR_X or f.data_loc != VERT:
+                raise X3dError("Feedback.add: DIR_X blocks at VERT are needed")
+        _lib.check(self.lib.x3d_particles_feedback_add(b.h, p.h, du.ptr, dv.ptr, dw.ptr, b._dims(VERT)))
+
+    def field(self):
+        """f itself, for tests and snapshots: the same passes into three zeroed blocks of the allocator's, which the caller
+        releases"""
+        al = self.particles.solver.backend.allocator
+        out = [al.get_block(DIR_X, VERT) for _ in range(3)]
+        for f in out:
+            f.fill(0.0)
+        self.add(*out)
+        return out
+
+    def records(self):
+        """(counts[9]: the first record of each colour and the number of occupied cells, cells[q], records[q, 8, 3]) in the
+        order of the colour lists; one host wait"""
+        p = self.particles
+        counts = _lib.ints(*([0] * 9))
+        cells, rec = np.zeros(p.n, dtype=np.uint32), np.zeros((p.n, 8, 3))
+        _lib.check(self.lib.x3d_particles_feedback_download(p.solver.backend.h, p.h, counts, cells.ctypes.data, rec.ctypes.data))
+        q = int(counts[8])
+        return np.array(list(counts), dtype=np.int64), cells[:q].copy(), rec[:q].copy()

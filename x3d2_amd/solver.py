@@ -167,6 +167,9 @@ class Solver:
         # optional forcing.Forcing(solver, cfg): BaseCase.substep then adds the band forcing to the right-hand side; None = no
         # forcing, and the sub-step is what it was
         self.forcing = None
+        # set by particles.Particles with two_way=True (particles.Feedback): BaseCase.substep then adds the particles' drag
+        # reaction to the right-hand side; None = one-way particles or none, and the sub-step is what it was
+        self.particle_feedback = None
         # keep_pressure / pressure (src/solver.f90:60-61, 705-714): the last pressure stays in a block of its own for the
         # snapshots (snapshot.Snapshots sets keep_pressure).  pressure_wanted: the fused driver keeps it only where the
         # case asks (BaseCase.step: the last sub-step of a step whose snapshot is due), see pressure_correction_fused
